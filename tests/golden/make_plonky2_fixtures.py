@@ -37,8 +37,27 @@ def copy_bin():
     shutil.copy(os.path.join(REF, d, "proof.bin"), os.path.join(OUT, "plonky2_near_random_CGZP_proof.bin"))
 
 
+def full_proofs():
+    """every golden proof of the reference with all 28 FRI query rounds, verbatim (tests/test_oracle_plonky2.py)"""
+    import glob
+    import gzip
+    cases = []
+    for d in sorted(glob.glob(os.path.join(REF, "near_bft_finality/proofs/*/*/"))):
+        if os.path.exists(os.path.join(d, "proof.json")):
+            cases.append((d, "proof.json", "verifier_data.json", "common_data.json"))
+    t = os.path.join(REF, "gnark-plonky2-verifier/testdata/test_circuit/")
+    cases.append((t, "proof_with_public_inputs.json", "verifier_only_circuit_data.json", "common_circuit_data.json"))
+    out = [{"source": os.path.relpath(d, REF), "proof": json.load(open(d + pj)), "verifier_data": json.load(open(d + vj)),
+            "common_data": json.load(open(d + cj))} for d, pj, vj, cj in cases]
+    path = os.path.join(OUT, "plonky2_reference_proofs_full.json.gz")
+    with gzip.GzipFile(path, "wb", compresslevel=9, mtime=0) as f:
+        f.write(json.dumps(out, separators=(",", ":")).encode())
+    print("full proofs", len(out), os.path.getsize(path))
+
+
 if __name__ == "__main__":
     copy_bin()
+    full_proofs()
     d = "near_bft_finality/proofs/random/CGZPhFRkL3NvmGaXWBc6N7qJD519EUe6vyNpaEyDe2Ev/"
     trim("near_random_CGZP", d + "proof.json", d + "verifier_data.json", d + "common_data.json")
     t = "gnark-plonky2-verifier/testdata/test_circuit/"

@@ -2,13 +2,13 @@
 Merkle paths to the caps, evaluation-domain order, FRI folding): pins oracle/poseidon_gl.py,
 oracle/poseidon_bn254.py and the Merkle conventions the GPU kernels are tested against."""
 import copy
-import glob
+import gzip
 import json
 import os
 
 import pytest
 
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 from oracle import plonky2_verifier as V
 
 FIX = ["plonky2_near_random_CGZP.json", "plonky2_gnark_test_circuit.json"]
@@ -47,15 +47,11 @@ def test_tampering_is_detected(what):
         V.verify(j["proof"], j["verifier_data"], j["common_data"])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree only exists in the build container")
 def test_all_reference_proofs_full_28_rounds():
-    R = "/root/reference/"
-    cases = []
-    for d in sorted(glob.glob(R + "near_bft_finality/proofs/*/*/")):
-        if os.path.exists(d + "proof.json"):
-            cases.append((d + "proof.json", d + "verifier_data.json", d + "common_data.json"))
-    t = R + "gnark-plonky2-verifier/testdata/test_circuit/"
-    cases.append((t + "proof_with_public_inputs.json", t + "verifier_only_circuit_data.json", t + "common_circuit_data.json"))
+    """the reference's four golden proofs, all 28 FRI query rounds (tests/golden/make_plonky2_fixtures.py: full_proofs)"""
+    with gzip.open(os.path.join(GOLDEN, "plonky2_reference_proofs_full.json.gz")) as f:
+        cases = json.load(f)
     assert len(cases) == 4
-    for pj, vj, cj in cases:
-        V.verify(json.load(open(pj)), json.load(open(vj)), json.load(open(cj)))
+    for c in cases:
+        assert len(c["proof"]["proof"]["opening_proof"]["query_round_proofs"]) == 28, c["source"]
+        V.verify(c["proof"], c["verifier_data"], c["common_data"])

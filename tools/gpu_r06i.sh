@@ -9,7 +9,6 @@ run stages ZKLC_STREAM=stages
 run fold ZKLC_STREAM=fold
 run fold_hdr ZKLC_STREAM=fold,hdr
 run all ZKLC_STREAM=fold,hdr,ahead
-run stages_q4 ZKLC_STREAM=stages GPU_MAX_HW_QUEUES=4
 run all2 ZKLC_STREAM=fold,hdr,ahead
 run stages2 ZKLC_STREAM=stages
 python - <<'PY'
