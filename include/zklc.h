@@ -325,7 +325,51 @@ int32_t zklc_plonky2_witness_program_create_from_container(zklc_ctx *ctx, const 
 int32_t zklc_plonky2_witness_run_from_container(const zklc_container *c, const uint64_t *input_values, uint32_t n_witnesses,
                                                 uint64_t *wires_out, uint64_t *pi_out, int32_t *status, char *err_out, uint32_t threads);
 
-/* ---- (c) BN254 ---------------------------------------------------------------
+/* ---- (b''') plonky2 verifier ---------------------------------------------------------------------------------------------
+ * Replaces `CircuitData::verify` / `VerifierCircuitData::verify` of the un-vendored plonky2 fork, called right after `prove` at
+ *   near_bft_finality/src/prove_block_data/primitives.rs:110,160 and header_bphash.rs:94 (`data.verify(proof)`),
+ *   the tests of near_bft_finality/src/prove_crypto/ed25519.rs:175-202, recursion.rs:124-153, sha256.rs:211-215,
+ * and the check a host owes the proofs that come back from remote workers (the NATS `OutputTask` of signatures.rs:144-274).
+ * The checks and their order are those of gnark-plonky2-verifier (verifier/verifier.go, fri/fri.go, plonk/plonk.go):
+ * format, proof of work, vanishing identity at zeta, then the query rounds in index order (per round: initial trees 0..3, then per
+ * FRI reduction its consistency check and its Merkle opening, then the final polynomial).  A proof's status is its first failed
+ * check.  The once-per-proof work (parse, transcript replay, gate constraints at zeta, reduced openings) runs on host threads;
+ * zklc_plonky2_verify_batch runs the query phase of the whole batch on the GPU (Merkle openings and FRI fold chains, one lane each),
+ * zklc_plonky2_verify_batch_host runs everything on the host.  Both give the same status for every proof. */
+typedef struct zklc_plonky2_verifier zklc_plonky2_verifier;
+#define ZKLC_PROOF_OK 0
+#define ZKLC_PROOF_BAD_FORMAT 1    /* a u64 >= p (a BN128 digest >= r), wrong public-input count, a sibling count that contradicts common data */
+#define ZKLC_PROOF_BAD_POW 2       /* the proof-of-work response has more than 64 - proof_of_work_bits bits */
+#define ZKLC_PROOF_BAD_VANISHING 3 /* vanishing(zeta) != Z_H(zeta) * t(zeta) for some challenge */
+#define ZKLC_PROOF_BAD_MERKLE 4    /* an initial-tree or commit-phase opening does not reach its cap */
+#define ZKLC_PROOF_BAD_FRI 5       /* fold consistency or final-polynomial mismatch */
+/* The circuit's common data (params, gates, gate_extra, k_is: the arguments of zklc_plonky2_circuit_create) and its verifier_only
+ * data: cap = 2^min(cap_height, degree_bits + rate_bits) digests of 32 bytes, digest = 32 bytes (the zklc_plonky2_verifier_data
+ * layout).  ctx may be NULL (the GPU buffers are made by the first zklc_plonky2_verify_batch; a verifier stays on that GPU).
+ * ZKLC_ERR_INVALID_ARG for parameters no proof can have or an unknown gate type.  Lookups and zero-knowledge (hiding) circuits are
+ * not supported: the parameters carry neither, so the caller refuses them (zklc_amd.plonky2.verifier does). */
+int32_t zklc_plonky2_verifier_create(zklc_ctx *ctx, const zklc_plonky2_params *params, const zklc_plonky2_gate *gates,
+                                     const uint64_t *gate_extra, uint32_t gate_extra_words, const uint64_t *k_is,
+                                     const uint8_t *cap, const uint8_t *digest, zklc_plonky2_verifier **out);
+/* the same for a circuit of zklc_plonky2_circuit_create: its creation arguments, and cap and digest from its commitment
+ * (replaces `data.verifier_data()` + `VerifierCircuitData` of the reference's call sites) */
+int32_t zklc_plonky2_verifier_create_from_circuit(zklc_ctx *ctx, zklc_plonky2_circuit *c, zklc_plonky2_verifier **out);
+void zklc_plonky2_verifier_destroy(zklc_plonky2_verifier *v);
+/* == zklc_plonky2_proof_bytes of the circuit */
+uint64_t zklc_plonky2_verifier_proof_bytes(const zklc_plonky2_verifier *v);
+/* n proofs of this circuit, each zklc_plonky2_verifier_proof_bytes long, concatenated (ProofWithPublicInputs::to_bytes()).
+ * status_out[i] = ZKLC_PROOF_* of proof i.  The return value is the status of the CALL (arguments, HIP, OOM); a rejected proof is
+ * not an error of the call.  The device buffers are the verifier's and only grow; host pointers, returns when the verdicts are in.
+ * One call at a time per verifier (its buffers are shared state): threads that verify concurrently use one verifier each. */
+int32_t zklc_plonky2_verify_batch(zklc_ctx *ctx, zklc_plonky2_verifier *v, const uint8_t *proofs, uint64_t n, int32_t *status_out);
+/* the same on the host only, 1 proof per task on min(n, nthreads) threads (0 = 16) */
+int32_t zklc_plonky2_verify_batch_host(zklc_plonky2_verifier *v, const uint8_t *proofs, uint64_t n, uint32_t nthreads,
+                                       int32_t *status_out);
+/* wall-clock milliseconds of the last zklc_plonky2_verify_batch: host stage, kernel A (Merkle openings), kernel B (FRI folds),
+ * total; returns the number of doubles written */
+uint32_t zklc_plonky2_verifier_last_timings(const zklc_plonky2_verifier *v, double *out_ms, uint32_t cap);
+
+/* ---- (c) BN254---------------------------------------------------------------
  * G1 multi-scalar multiplication sum_i scalars[i] * points[i].
  * Replaces gnark-crypto `bn254.G1Affine.MultiExp` (un-vendored; gnark-plonky2-verifier/go.mod:9)
  * called from `groth16.Prove` at gnark-plonky2-verifier/cmd/web-api.go:77.

@@ -79,6 +79,15 @@ _SIGS = {
     "zklc_plonky2_circuit_destroy": (None, [ctypes.c_void_p]),
     "zklc_plonky2_verifier_data": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p]),
     "zklc_plonky2_proof_bytes": (ctypes.c_uint64, [ctypes.c_void_p]),
+    # plonky2 verifier
+    "zklc_plonky2_verifier_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, _u8p,
+                                                      _u8p, ctypes.POINTER(ctypes.c_void_p)]),
+    "zklc_plonky2_verifier_create_from_circuit": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "zklc_plonky2_verifier_destroy": (None, [ctypes.c_void_p]),
+    "zklc_plonky2_verifier_proof_bytes": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "zklc_plonky2_verify_batch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p]),
+    "zklc_plonky2_verify_batch_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p]),
+    "zklc_plonky2_verifier_last_timings": (ctypes.c_uint32, [ctypes.c_void_p, _u8p, ctypes.c_uint32]),
     "zklc_plonky2_prove": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64,
                                             ctypes.POINTER(ctypes.c_uint64)]),
     "zklc_plonky2_prove_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64,

@@ -1937,3 +1937,33 @@ extern "C" int32_t zklc_plonky2_prove(zklc_ctx *ctx, zklc_plonky2_circuit *c, co
     ZKLC_HIP(ctx, hipMemcpyAsync(c->d_wire_vals, wires, bytes, hipMemcpyHostToDevice, ctx->stream));
     return zklc_plonky2_prove_dev(ctx, ctx->stream, c, c->d_wire_vals, public_inputs, proof_out, proof_cap, proof_len);
 }
+
+// What a verifier of this circuit needs besides its commitment (csrc/plonky2_verifier_host.cpp,
+// zklc_plonky2_verifier_create_from_circuit): the arguments of zklc_plonky2_circuit_create it was made from, the gate_extra table
+// and k_is read back from HBM.  gate_extra holds the CosetInterpolationGate tables only (weights, then subgroup points), so its
+// length is the end of the last such table.
+int32_t p2_circuit_verifier_args(zklc_plonky2_circuit *c, zklc_plonky2_params *params, std::vector<zklc_plonky2_gate> *gates,
+                                 std::vector<uint64_t> *extra, std::vector<uint64_t> *k_is) {
+    zklc_ctx *ctx = c->ctx;
+    *params = c->P;
+    gates->resize(c->gates.size());
+    size_t extra_words = 0;
+    for (size_t i = 0; i < c->gates.size(); i++) {
+        const p2_gate &g = c->gates[i];
+        zklc_plonky2_gate &o = (*gates)[i];
+        o.type = g.type;
+        for (int k = 0; k < 4; k++) o.p[k] = g.p[k];
+        o.selector_index = g.selector_index;
+        o.group_start = g.group_start;
+        o.group_end = g.group_end;
+        o.extra_off = g.extra_off;
+        if (g.type == P2_COSET_INTERPOLATION) extra_words = std::max(extra_words, (size_t)g.extra_off + (2u << g.p[0]));
+    }
+    extra->assign(extra_words, 0);
+    k_is->assign(c->P.num_routed_wires, 0);
+    ZKLC_HIP(ctx, hipSetDevice(ctx->device));
+    if (extra_words) ZKLC_HIP(ctx, zklc_readback_async(extra->data(), c->d_extra, extra_words * 8, ctx->stream));
+    ZKLC_HIP(ctx, zklc_readback_async(k_is->data(), c->d_kis, k_is->size() * 8, ctx->stream));
+    ZKLC_HIP(ctx, zklc_stream_wait(ctx->stream));
+    return ZKLC_OK;
+}

@@ -17,12 +17,27 @@ def vec_u32_to_u8(words):
 
 
 class BlockHashProver:
-    def __init__(self, ctx, sha=None, recursion=None):
+    def __init__(self, ctx, sha=None, recursion=None, verify=False):
+        """verify=True: the header-hash proof is checked by the native verifier before it is returned, where the reference calls
+        `data.verify(proof)` (header_bphash.rs:94); a proof that does not verify raises plonky2.verifier.ProofRejected"""
         from .plonky2 import HASH_GL
         from .plonky2.recursion import RecursionProver
         from .plonky2.sha256 import Sha256Prover
+        self.ctx, self.verify = ctx, verify
+        self._verifiers = {}
         self.sha = sha or Sha256Prover(ctx, HASH_GL)
         self.recursion = recursion or RecursionProver(ctx, HASH_GL)
+
+    def _verify(self, triple):
+        """the native verifier of the triple's circuit (one per circuit digest), on this prover's context"""
+        import json
+        from .plonky2.verifier import Verifier
+        common, vd, proof = triple
+        key = json.dumps(vd, sort_keys=True)
+        v = self._verifiers.get(key)
+        if v is None:
+            v = self._verifiers[key] = Verifier(self.ctx, common, vd)
+        v.verify(proof)
 
     def _sha(self, msg, digest):
         (common, vd), proof = self.sha.sha256_proof_u32(msg, digest)
@@ -55,9 +70,10 @@ class BlockHashProver:
         p2 = self._sha(inner_rest, hashlib.sha256(inner_rest).digest())
         p3 = self.prove_sub_hashes_u32(True, True, p1[2]["public_inputs"], p2[2]["public_inputs"], None, p1, p2)
         p4 = self.prove_sub_hashes_u32(True, False, p3[2]["public_inputs"], list(bytes(prev_hash)), header_hash, p3, None)
-        if public_inputs is not None:
-            return self._rec(p4, None, [int(x) for x in public_inputs])
-        return p4
+        out = self._rec(p4, None, [int(x) for x in public_inputs]) if public_inputs is not None else p4
+        if self.verify:
+            self._verify(out)
+        return out
 
     def prove_bp_hash(self, bp_hash, validators):
         """header_bphash.rs:121-139: bp_hash = sha256(borsh(Vec<ValidatorStake>)) = sha256(le32(len) || entries)"""
@@ -65,5 +81,8 @@ class BlockHashProver:
         return self._sha(data, bp_hash)
 
     def close(self):
+        for v in self._verifiers.values():
+            v.close()
+        self._verifiers = {}
         self.sha.close()
         self.recursion.close()

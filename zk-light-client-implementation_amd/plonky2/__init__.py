@@ -8,3 +8,4 @@ from . import gates  # noqa: F401
 from .builder import CircuitBuilder, CircuitData, Target, standard_recursion_config, wide_ecc_config  # noqa: F401
 from . import serialization  # noqa: F401
 from .prover import Prover, poseidon_gate_rows, HASH_GL, HASH_BN128  # noqa: F401
+from .verifier import Verifier, ProofRejected, native_arguments_from_common  # noqa: F401

@@ -62,6 +62,9 @@ class Prover:
         self.proof_bytes = int(self._lib.zklc_plonky2_proof_bytes(h))
 
     def close(self):
+        if getattr(self, "_verifier", None) is not None:
+            self._verifier.close()
+            self._verifier = None
         if getattr(self, "_h", None):
             self._lib.zklc_plonky2_circuit_destroy(self._h)
             self._h = None
@@ -117,6 +120,14 @@ class Prover:
                                               out.ctypes.data, out.size, ctypes.byref(ln))
         self.ctx._check(rc)
         return bytes(out[:ln.value])
+
+    def verify(self, proof):
+        """`data.verify(proof)`: the native verifier of this circuit (made on first use, on this prover's context) checks `proof`
+        (bytes or the proof.json dict); raises verifier.ProofRejected when it does not verify"""
+        if getattr(self, "_verifier", None) is None:
+            from .verifier import Verifier
+            self._verifier = Verifier.from_prover(self)
+        self._verifier.verify(proof)
 
     def last_challenges(self):
         buf = np.zeros(64, dtype=np.uint64)

@@ -112,8 +112,11 @@ def eq_array_circuit(n):
 class PrimitiveProver:
     """the three functions with the reference's signatures: byte strings in, (common, verifier_only, proof) out"""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, verify=False):
+        """verify=True: every proof is checked by the native verifier before it is returned, where the reference calls
+        `data.verify(proof)` (primitives.rs:110,160); a proof that does not verify raises plonky2.verifier.ProofRejected"""
         self.ctx = ctx
+        self.verify = verify
         self._cache = {}
 
     def _prove(self, key, build, values):
@@ -131,7 +134,10 @@ class PrimitiveProver:
             ent = self._cache[key] = (data, aux["t"], prover, data.common_data(), prover.verifier_data())
         data, targets, prover, common, vd = ent
         wires, pis = data.generate_witness_native([dict(zip(targets, values))])
-        return common, vd, prover.prove(wires[0], [int(x) for x in pis[0]])
+        proof = prover.prove(wires[0], [int(x) for x in pis[0]])
+        if self.verify:
+            prover.verify(proof)
+        return common, vd, proof
 
     def two_thirds(self, value1, value2):
         assert len(value1) == len(value2) == STAKE_BYTES + 1
