@@ -431,6 +431,44 @@ int32_t zklc_bn254_pairing_check(zklc_ctx *ctx, const uint64_t *g1, const uint64
 int32_t zklc_bn254_pairing_check_dev(zklc_ctx *ctx, void *stream, const uint64_t *d_g1, const uint64_t *d_g2, uint32_t k,
                                      uint32_t batch, uint32_t *d_is_one, uint64_t *d_gt_out);
 
+/* Batched Groth16 verification, safe on untrusted proof bytes: replaces `groth16.Verify` (gnark-plonky2-verifier/cmd/web-api.go:84)
+ * TOGETHER WITH the validation in front of it (`proof.isValid()`, the decoding of `proof.ReadFrom`, and the decompression at the
+ * head of the contract's `verifyCompressedProof`, contracts/hardhat/contracts/Verifier.sol:427-449).  Per proof: decode, coordinates
+ * reduced, A / C / B on their curves, B in the r-torsion subgroup of the twist, kSum = K[0] + sum_i x_i K[i + 1], and
+ * e(A, B) e(C, -delta) e(kSum, -gamma) e(alpha, -beta) == 1.  status_out[i] is the FIRST failing class in this fixed order: */
+typedef struct zklc_groth16_verifier zklc_groth16_verifier;
+#define ZKLC_G16_OK 0
+#define ZKLC_G16_BAD_ENCODING 1     /* a coordinate >= p; compressed form: an x >= p, or a B whose hint bit selects a root that does not exist */
+#define ZKLC_G16_INFINITY 2         /* A, B or C all zero */
+#define ZKLC_G16_NOT_ON_CURVE 3     /* A, then C, then B; compressed form: an x with no y */
+#define ZKLC_G16_NOT_IN_SUBGROUP 4  /* B on the twist but not of order r */
+#define ZKLC_G16_PAIRING 5          /* the points are valid group elements and the pairing equation does not hold */
+#define ZKLC_G16_COMPRESSED 1u      /* flags: proofs are the 4 words of the contract's compressProof, not the 8 of WriteRawTo */
+/* The verifying key: alpha1 (8 u64), beta2 / gamma2 / delta2 (16 u64 each), K[(n_public + 1) x 8], affine points in gnark-crypto's
+ * memory layout (Montgomery limbs, as for the multi-exponentiations and the pairing entries).  The key is validated once, here:
+ * coordinates reduced, on the curve, the G2 points in the r-torsion subgroup, alpha / beta / gamma / delta finite (a K point may be
+ * the point at infinity); ZKLC_ERR_INVALID_ARG otherwise, and for n_public > 4096.  Also built here: the negated G2 points and a
+ * fixed-base table of K[1..] (rows d 16^w K[i], 75 KiB per public input) so that the fold of a batch has no doublings.
+ * ctx may be NULL (host only; the GPU buffers are made by the first zklc_groth16_verify_batch and the verifier stays on that GPU).
+ * No commitment extension (the reference's key has none). */
+int32_t zklc_groth16_verifier_create(zklc_ctx *ctx, const uint64_t *alpha1, const uint64_t *beta2, const uint64_t *gamma2,
+                                     const uint64_t *delta2, const uint64_t *K, uint32_t n_public, zklc_groth16_verifier **out);
+void zklc_groth16_verifier_destroy(zklc_groth16_verifier *v);
+/* proofs: n x 256 bytes, the uncompressed encoding of `proof.WriteRawTo` (web-api.go:90-98): eight 32-byte big-endian words A.x, A.y,
+ * B.x1, B.x0, B.y1, B.y0, C.x, C.y; with ZKLC_G16_COMPRESSED n x 128 bytes: A, B.c1, B.c0, C as `compressProof` writes them.
+ * public_inputs: n x n_public x 4 u64, regular form; a value >= r is reduced (it is not an error).  The return value is the status
+ * of the CALL (arguments, HIP, OOM; n > 2^24 is ZKLC_ERR_INVALID_ARG); a rejected proof is a status, not an error of the call.
+ * Host pointers; one upload, two kernels, one read-back; returns when the verdicts are in.  The device buffers are the verifier's
+ * and only grow.  One call at a time per verifier: threads that verify concurrently use one verifier each. */
+int32_t zklc_groth16_verify_batch(zklc_ctx *ctx, zklc_groth16_verifier *v, const uint8_t *proofs, const uint64_t *public_inputs,
+                                  uint64_t n, uint32_t flags, int32_t *status_out);
+/* the same on the host only (the same lane functions compiled for the host), 1 proof per task on min(n, nthreads) threads (0 = 16) */
+int32_t zklc_groth16_verify_batch_host(zklc_groth16_verifier *v, const uint8_t *proofs, const uint64_t *public_inputs, uint64_t n,
+                                       uint32_t nthreads, uint32_t flags, int32_t *status_out);
+/* milliseconds of the last zklc_groth16_verify_batch: upload, validation / kSum kernel, pairing kernel (device events), total (wall
+ * clock); returns the number of doubles written */
+uint32_t zklc_groth16_verifier_last_timings(const zklc_groth16_verifier *v, double *out_ms, uint32_t cap);
+
 /* NTT over the BN254 scalar field Fr.  Replaces gnark-crypto `fft.Domain.FFT / FFTInverse` (ecc/bn254/fr/fft, un-vendored)
  * inside `groth16.Prove` (gnark-plonky2-verifier/cmd/web-api.go:77).  data: 2^log_n elements in gnark-crypto's memory layout
  * (x * 2^256 mod r, 4 little-endian u64), transformed in place.  values[k] = sum_j coeffs[j] w^(jk), w = rootOfUnity^(2^28/n);

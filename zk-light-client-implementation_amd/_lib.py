@@ -68,6 +68,14 @@ _SIGS = {
     "zklc_bn254_pairing_check": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p]),
     "zklc_bn254_pairing_check_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32,
                                                       _u8p, _u8p]),
+    # Groth16 verifier
+    "zklc_groth16_verifier_create": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint32,
+                                                      ctypes.POINTER(ctypes.c_void_p)]),
+    "zklc_groth16_verifier_destroy": (None, [ctypes.c_void_p]),
+    "zklc_groth16_verify_batch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p]),
+    "zklc_groth16_verify_batch_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                                        _u8p]),
+    "zklc_groth16_verifier_last_timings": (ctypes.c_uint32, [ctypes.c_void_p, _u8p, ctypes.c_uint32]),
     "zklc_bn254_fr_ntt": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,

@@ -352,3 +352,132 @@ class Groth16Verifier:
         g2 = np.array([[g2_words(b)] + self.neg_g2_words], dtype=np.uint64)
         ok, _ = self.ctx.bn254_pairing_check(g1, g2, 4)
         return bool(int(ok[0]))
+
+
+# ---------------------------------------------------------------------------------------------- native batched verifier
+G16_OK, G16_BAD_ENCODING, G16_INFINITY, G16_NOT_ON_CURVE, G16_NOT_IN_SUBGROUP, G16_PAIRING = range(6)
+G16_STATUS_NAMES = {G16_OK: "OK", G16_BAD_ENCODING: "BAD_ENCODING", G16_INFINITY: "INFINITY", G16_NOT_ON_CURVE: "NOT_ON_CURVE",
+                    G16_NOT_IN_SUBGROUP: "NOT_IN_SUBGROUP", G16_PAIRING: "PAIRING"}
+G16_COMPRESSED = 1
+
+
+class ProofRejected(ValueError):
+    """a proof the native verifier rejected; `status` is its G16_* class"""
+
+    def __init__(self, status):
+        self.status = int(status)
+        super().__init__("groth16 proof rejected: %s" % G16_STATUS_NAMES.get(self.status, str(self.status)))
+
+
+class NativeGroth16Verifier:
+    """`groth16.Verify` with the validation in front of it as ONE call of the C ABI (zklc_groth16_verify_batch, include/zklc.h):
+    decoding, reduced-coordinate / on-curve / subgroup tests, the public-input fold and the pairing product run in the library,
+    on the GPU (`verify_batch`) or on host threads (`verify_batch_host`), with one status per proof.  ctx may be None (host only).
+
+    vk: the dictionary `Groth16Verifier` takes.  A key with an invalid point raises ZklcError (ZKLC_ERR_INVALID_ARG)."""
+    STATUS_NAMES = G16_STATUS_NAMES
+
+    def __init__(self, ctx, vk):
+        import ctypes
+        from . import _lib
+        self.ctx = ctx
+        self._lib = _lib.load()
+        self.n_public = len(vk["K"]) - 1
+        if self.n_public < 0:
+            raise ValueError("verifying key without K[0]")
+        arr = lambda words: np.ascontiguousarray(np.array(words, dtype=np.uint64).reshape(-1))
+        al, be, ga, de = arr(g1_words(vk["alpha1"])), arr(g2_words(vk["beta2"])), arr(g2_words(vk["gamma2"])), arr(g2_words(vk["delta2"]))
+        k = arr([g1_words(p) for p in vk["K"]])
+        h = ctypes.c_void_p()
+        rc = self._lib.zklc_groth16_verifier_create(ctx._h if ctx is not None else None, al.ctypes.data, be.ctypes.data, ga.ctypes.data,
+                                                    de.ctypes.data, k.ctypes.data, self.n_public, ctypes.byref(h))
+        if rc != 0:
+            raise _lib.ZklcError(rc, "zklc_groth16_verifier_create")
+        self._v = h
+
+    def close(self):
+        v, self._v = getattr(self, "_v", None), None
+        if v:
+            self._lib.zklc_groth16_verifier_destroy(v)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _pack(self, proofs, public_inputs, compressed):
+        words, size = (4, 128) if compressed else (8, 256)
+        raw = []
+        for p in proofs:
+            if isinstance(p, (bytes, bytearray, memoryview)):
+                p = bytes(p)
+                if len(p) != size:
+                    raise ValueError("a%s Groth16 proof has %d bytes, got %d" % (" compressed" if compressed else "n uncompressed", size, len(p)))
+            else:
+                p = [int(x) for x in p]
+                if len(p) != words:
+                    raise ValueError("a%s Groth16 proof has %d words, got %d" % (" compressed" if compressed else "n uncompressed", words, len(p)))
+                if any(x < 0 or x >> 256 for x in p):
+                    raise ValueError("a proof word does not fit 256 bits")
+                p = b"".join(x.to_bytes(32, "big") for x in p)
+            raw.append(p)
+        if len(public_inputs) != len(raw):
+            raise ValueError("%d proofs, %d public-input vectors" % (len(raw), len(public_inputs)))
+        pi = np.zeros((len(raw), max(self.n_public, 1), 4), dtype=np.uint64)
+        for i, xs in enumerate(public_inputs):
+            if len(xs) != self.n_public:
+                raise ValueError("invalid witness size: %d public inputs, the key has %d" % (len(xs), self.n_public))
+            for j, x in enumerate(xs):
+                x = int(x)
+                if x < 0 or x >> 256:
+                    x %= R
+                pi[i, j] = [(x >> (64 * t)) & _M64 for t in range(4)]
+        if self.n_public == 0:
+            pi = pi[:, :0]
+        return np.frombuffer(b"".join(raw), dtype=np.uint8), np.ascontiguousarray(pi)
+
+    def _run(self, proofs, public_inputs, compressed, host, nthreads=0):
+        from . import _lib
+        if self._v is None:
+            raise ValueError("verifier is closed")
+        proofs = list(proofs)
+        buf, pi = self._pack(proofs, list(public_inputs), compressed)
+        n = len(proofs)
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        if n == 0:
+            return []
+        flags = G16_COMPRESSED if compressed else 0
+        if host:
+            rc = self._lib.zklc_groth16_verify_batch_host(self._v, buf.ctypes.data, pi.ctypes.data, n, nthreads, flags, out.ctypes.data)
+        else:
+            if self.ctx is None:
+                raise ValueError("verify_batch needs a Context; a verifier without one has verify_batch_host")
+            rc = self._lib.zklc_groth16_verify_batch(self.ctx._h, self._v, buf.ctypes.data, pi.ctypes.data, n, flags, out.ctypes.data)
+        if rc != 0:
+            detail = ""
+            if not host:
+                detail = (self._lib.zklc_last_hip_error(self.ctx._h) or b"").decode()
+            raise _lib.ZklcError(rc, detail)
+        return [int(s) for s in out[:n]]
+
+    def verify_batch(self, proofs, public_inputs, compressed=False):
+        """proofs: each 256 (compressed: 128) bytes or the list of 8 (4) integers; public_inputs: one list of n_public integers per
+        proof.  -> the list of G16_* statuses, on the GPU"""
+        return self._run(proofs, public_inputs, compressed, host=False)
+
+    def verify_batch_host(self, proofs, public_inputs, compressed=False, nthreads=0):
+        return self._run(proofs, public_inputs, compressed, host=True, nthreads=nthreads)
+
+    def verify(self, proof, public_inputs, compressed=False):
+        """one proof, on the GPU when the verifier has a context and on the host otherwise: True, or raises ProofRejected(status)"""
+        st = self._run([proof], [public_inputs], compressed, host=self.ctx is None)[0]
+        if st != G16_OK:
+            raise ProofRejected(st)
+        return True
+
+    def last_timings(self):
+        """milliseconds of the last verify_batch: upload, validation / kSum kernel, pairing kernel, total"""
+        out = np.zeros(4, dtype=np.float64)
+        k = self._lib.zklc_groth16_verifier_last_timings(self._v, out.ctypes.data, 4)
+        return dict(zip(("upload", "validate_ksum_kernel", "pairing_kernel", "total")[:k], out[:k].tolist()))
