@@ -142,3 +142,95 @@ def test_hash_no_pad_kat_through_merkle(zctx):
     st = np.zeros((1, 12), dtype=np.uint64)
     st[0, :3] = kat["in"]
     assert [int(x) for x in zctx.poseidon_gl_permute(st)[0, :4]] == kat["out"]
+
+
+# ---- edge operands through the public kernels: the values at which a reduction can go wrong (tests/devsim_vectors.py) instead of
+# uniform random data, which never takes the rare branches of the multiply-reduce
+def edge_polys(n, seed):
+    """six polynomials of n coefficients: alphabet draws, all p - 1, the powers of two 2^k, one non-zero coefficient at 0 / 1 / n - 1"""
+    import random
+    import devsim_vectors as DV
+    rng = random.Random(seed)
+    polys = [[rng.choice(DV.CANON) for _ in range(n)], [P - 1] * n, [pow(2, k, P) for k in range(n)]]
+    for idx, v in ((0, P - 1), (1 % n, 2**32), (n - 1, 1)):
+        d = [0] * n
+        d[idx] = v
+        polys.append(d)
+    return np.array(polys, dtype=np.uint64)
+
+
+@pytest.mark.parametrize("log_n", [4, 9, 13, 14])
+def test_ntt_edge_inputs_match_oracle(zctx, log_n):
+    n = 1 << log_n
+    polys = edge_polys(n, log_n)
+    br = bitrev_fast(log_n)
+    for a in (polys[:3], polys[3:]):           # batch 3
+        want = cport.gl_ntt(a, nthreads=4)
+        want_inv = cport.gl_ntt(a, inverse=True, nthreads=4)
+        assert np.array_equal(zctx.gl_ntt(a), want)
+        assert np.array_equal(zctx.gl_ntt(a, flags=INV), want_inv)
+        assert np.array_equal(zctx.gl_ntt(a, flags=OUT_BR), want[:, br])
+        assert np.array_equal(zctx.gl_ntt(np.ascontiguousarray(a[:, br]), flags=IN_BR), want)
+        assert np.array_equal(zctx.gl_ntt(np.ascontiguousarray(a[:, br]), flags=INV | IN_BR), want_inv)
+        assert np.array_equal(zctx.gl_ntt(a, flags=INV | OUT_BR), want_inv[:, br])
+    # a single coefficient 1 at index 0 transforms to all ones; all p - 1 to (-n, 0, 0, ...)
+    assert np.array_equal(cport.gl_ntt(polys[1:2], nthreads=1)[0], np.array([(P - n) % P] + [0] * (n - 1), dtype=np.uint64))
+
+
+@pytest.mark.parametrize("log_n,rate_bits", [(3, 3), (9, 3), (11, 3)])
+def test_lde_edge_inputs_match_oracle(zctx, log_n, rate_bits):
+    """the alphabet polynomials, and one whose coefficient j is built so that its multiplication by the coset scale 7^j takes a rare
+    branch of the reduction: the borrow (low half of the product tiny; ~2^-33 per product under uniform data), or, for the small
+    scales 7^j < 2^40 whose products have no top word to borrow, the result >= p without a carry (~2^-32)"""
+    import random
+    import devsim_vectors as DV
+    n = 1 << log_n
+    rng = random.Random(40 + log_n)
+    hard, taken = [], 0
+    for j in range(n):
+        m = pow(7, j, P)
+        c = DV.borrow_partner(m, rng.choice([1, 2, 3, 5]))
+        if c >= P or not DV.mul_model(c, m)[1]:
+            c = DV.ge_p_partner_small(m) if 1 < m < 2**32 else DV.ge_p_partner(m) if 1 < m < 2**40 else None
+        if c is None or c >= P:
+            c = rng.choice(DV.CANON)
+        r = DV.mul_model(c, m)
+        taken += r[1] or r[3]
+        hard.append(c)
+    assert taken >= n - 2, taken
+    polys = np.concatenate([edge_polys(n, 100 + log_n), np.array([hard], dtype=np.uint64)])
+    want = cport.gl_lde(polys, rate_bits, 7, nthreads=4)
+    assert np.array_equal(zctx.gl_lde(polys, rate_bits, 7), want)
+    assert np.array_equal(zctx.gl_lde(polys, rate_bits, 7, flags=OUT_BR), want[:, bitrev_fast(log_n + rate_bits)])
+    w = gl.root_of_unity(log_n + rate_bits)
+    for k in [0, 1, (n << rate_bits) - 1]:
+        assert int(want[6, k]) == gl.eval_poly(hard, 7 * pow(w, k, P) % P)
+
+
+def test_poseidon_permute_edge_states(zctx):
+    import devsim_vectors as DV
+    states = DV.poseidon_states(256, seed=21, loose=False)
+    out = zctx.poseidon_gl_permute(np.array(states, dtype=np.uint64))
+    for s, o in zip(states, out):
+        want = pg.permute(s)
+        assert [int(x) for x in o] == want == cport.poseidon_gl_permute(s)
+
+
+@pytest.mark.parametrize("width", [5, 9, 135])
+@pytest.mark.parametrize("cap", [0, 2])
+def test_merkle_commit_edge_leaves(zctx, width, cap):
+    import random
+    import devsim_vectors as DV
+    rng = random.Random(width * 7 + cap)
+    log_leaves = 6
+    mat = np.array([[rng.choice(DV.CANON) for _ in range(1 << log_leaves)] for _ in range(width)], dtype=np.uint64)
+    mat[0, :] = P - 1
+    mat[width - 1, 1::2] = 0
+    cap_gpu, levels = zctx.gl_merkle_commit(mat, cap)
+    want = cport.gl_merkle_commit(mat, cap, nthreads=4)
+    assert len(levels) == len(want)
+    for g, w in zip(levels, want):
+        assert np.array_equal(g, w)
+    leaves = [[int(mat[p, i]) for p in range(width)] for i in range(1 << log_leaves)]
+    cap_py, _ = pg.merkle_tree(leaves, cap)
+    assert [[int(x) for x in d] for d in cap_gpu] == cap_py

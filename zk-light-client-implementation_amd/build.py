@@ -66,5 +66,32 @@ def build(verbose=True, force=False):
     return LIB
 
 
+DEVSIM_DIR = os.path.join(HERE, "..", "tests", "devsim")
+DEVSIM_SRC = os.path.join(DEVSIM_DIR, "devsim.hip")
+DEVSIM_LIB = os.path.join(DEVSIM_DIR, "libdevsim.so")
+
+
+def devsim_sources():
+    return [DEVSIM_SRC, os.path.abspath(__file__)] + [p for ext in ("*.cuh", "*.h", "*.inc") for p in glob.glob(os.path.join(CSRC, ext))]
+
+
+def devsim_is_current():
+    return os.path.exists(DEVSIM_LIB) and os.path.getmtime(DEVSIM_LIB) >= _newest(devsim_sources())
+
+
+def build_devsim(verbose=True, force=False):
+    """tests/devsim/libdevsim.so: the arithmetic headers behind one-lane-per-tuple test kernels (test infrastructure, the device twin
+    of tests/hostsim; never part of libzklc_mi355.so).  Same compiler, same FLAGS as the library, so the lane functions are lowered
+    the way the product's are."""
+    if force or not devsim_is_current():
+        r = subprocess.run([HIPCC] + FLAGS + ["-shared", DEVSIM_SRC, "-o", DEVSIM_LIB], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (DEVSIM_SRC, r.stdout, r.stderr))
+        if verbose:
+            print("[zklc build] built", DEVSIM_LIB, file=sys.stderr)
+    return DEVSIM_LIB
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
+    build_devsim(force="--force" in sys.argv)
