@@ -151,7 +151,7 @@ ZKLC_HD fe fe_sqr_impl(const fe &f) {
     for (int i = 0; i < 10; i++) {
         f2[i] = 2 * f.v[i];
         f19[i] = 19 * f.v[i];
-        f38[i] = 38 * f.v[i];
+        f38[i] = (i & 1) ? 38 * f.v[i] : 0;      // only the odd limbs (25 bits) are ever taken times 38; 38 * a 26-bit limb overflows
     }
     i64 h[10];
 #pragma unroll

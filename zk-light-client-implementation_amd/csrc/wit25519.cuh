@@ -5,7 +5,8 @@
 // square-and-multiply; the critical path of the Ed25519 circuit's witness holds 318 inversions and 1 272 multiplications, so on
 // the device these run here instead: fully unrolled word arithmetic, and the inversions / square roots on the radix-2^25.5
 // field code the signature-verification kernel uses (fe25519.cuh: addition chains, 11 multiplications + 254 squarings).
-// Results are the canonical ones, i.e. identical to the generic path (checked on the CPU in tests/test_hostsim_ed25519.py).
+// Results are the canonical ones, i.e. identical to the generic path (checked against Python integers on edge operands: on the
+// CPU in tests/test_witops_host.py, on the device in tests/test_gpu_witops.py).
 #pragma once
 #include "fe25519.cuh"
 

@@ -41,7 +41,7 @@ def _recover_x(y, sign):
     if (x * x - xx) % P25519:
         raise ValueError("not a curve point")
     if (x & 1) != sign:
-        x = P25519 - x
+        x = (P25519 - x) % P25519       # x = 0 (y = +-1) stays 0, canonical, as curve25519-dalek's conditional negation leaves it
     return x
 
 
