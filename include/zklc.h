@@ -469,6 +469,39 @@ int32_t zklc_groth16_verify_batch_host(zklc_groth16_verifier *v, const uint8_t *
  * clock); returns the number of doubles written */
 uint32_t zklc_groth16_verifier_last_timings(const zklc_groth16_verifier *v, double *out_ms, uint32_t cap);
 
+/* Batched decoding and validation of point arrays in gnark-crypto's own encoding: the A, B1, Z, K (G1) and B2 (G2) arrays of a
+ * Groth16 proving key file (`pk.WriteRawTo` / `pk.WriteTo`, read back by `pk.ReadFrom`: gnark-plonky2-verifier/verifier/util.go:
+ * 172-216, 337-389).  Replaces gnark-crypto `G1Affine.SetBytes` / `G2Affine.SetBytes` in the decoder's loop (ecc/bn254/marshal.go,
+ * un-vendored) and establishes the precondition of the multi-exponentiations above (points on the curve), on the device.
+ * bytes: n slots of fixed stride, the file's bytes as they are -- raw: G1 64 bytes X | Y, G2 128 bytes X.A1 | X.A0 | Y.A1 | Y.A0,
+ * 32-byte big-endian coordinates, the two top bits of the first byte 00 (or 01: infinity); with ZKLC_POINTS_COMPRESSED: G1 32
+ * bytes, G2 64 bytes, x only, top bits 10 / 11 = y is the lexicographically smaller / larger root (Fp2 ordered by A1, by A0 when
+ * A1 = 0), 01 = infinity.  This is NOT the `compressProof` format of ZKLC_G16_COMPRESSED.
+ * words: n x 8 (G1) / n x 16 (G2) u64, the layout the multi-exponentiations read; all zero for every point whose status is not OK.
+ * status[i] (u32) is the FIRST failing class of point i in this fixed order: */
+#define ZKLC_POINT_OK 0
+#define ZKLC_POINT_INFINITY 1         /* a valid point, not an error: flag 01 with a zero payload, or an uncompressed (0, 0) */
+#define ZKLC_POINT_BAD_ENCODING 2     /* a coordinate >= p; flag 01 with non-zero coordinate bits; a flag of the other encoding */
+#define ZKLC_POINT_NOT_ON_CURVE 3     /* fails the curve equation; compressed: an x with no y */
+#define ZKLC_POINT_NOT_IN_SUBGROUP 4  /* G2 with ZKLC_POINTS_CHECK_SUBGROUP: on the twist, not of order r (G1 has cofactor 1) */
+#define ZKLC_POINTS_COMPRESSED 1u     /* flags */
+#define ZKLC_POINTS_CHECK_SUBGROUP 2u /* G2 only */
+/* summary: 4 u64 -- points OK, points at infinity, points rejected (status >= 2), index of the first rejected point (all-ones: none).
+ * The *_dev entries only enqueue (one lane per point, 256 lanes per workgroup; the membership test is a second kernel over the
+ * decoded words); the caller reads statuses and summary back.  d_bytes and d_words must be 16-byte aligned, n <= 2^31.  The return
+ * value is the status of the CALL: ZKLC_ERR_INVALID_ARG for a misaligned or missing pointer, unknown flag bits, or
+ * ZKLC_POINTS_CHECK_SUBGROUP on G1; a rejected point is a status, not an error of the call. */
+int32_t zklc_bn254_g1_decode_dev(zklc_ctx *ctx, void *stream, const uint8_t *d_bytes, uint64_t n, uint32_t flags, uint64_t *d_words,
+                                 uint32_t *d_status, uint64_t *d_summary);
+int32_t zklc_bn254_g2_decode_dev(zklc_ctx *ctx, void *stream, const uint8_t *d_bytes, uint64_t n, uint32_t flags, uint64_t *d_words,
+                                 uint32_t *d_status, uint64_t *d_summary);
+/* the same on the host only (the same lane functions compiled for the host) on min(n / 256, nthreads) threads (0 = 16): host
+ * pointers with the same alignment rule, no GPU and no context needed */
+int32_t zklc_bn254_g1_decode_host(const uint8_t *bytes, uint64_t n, uint32_t flags, uint32_t nthreads, uint64_t *words,
+                                  uint32_t *status, uint64_t *summary);
+int32_t zklc_bn254_g2_decode_host(const uint8_t *bytes, uint64_t n, uint32_t flags, uint32_t nthreads, uint64_t *words,
+                                  uint32_t *status, uint64_t *summary);
+
 /* NTT over the BN254 scalar field Fr.  Replaces gnark-crypto `fft.Domain.FFT / FFTInverse` (ecc/bn254/fr/fft, un-vendored)
  * inside `groth16.Prove` (gnark-plonky2-verifier/cmd/web-api.go:77).  data: 2^log_n elements in gnark-crypto's memory layout
  * (x * 2^256 mod r, 4 little-endian u64), transformed in place.  values[k] = sum_j coeffs[j] w^(jk), w = rootOfUnity^(2^28/n);

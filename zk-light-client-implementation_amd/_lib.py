@@ -76,6 +76,11 @@ _SIGS = {
     "zklc_groth16_verify_batch_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                         _u8p]),
     "zklc_groth16_verifier_last_timings": (ctypes.c_uint32, [ctypes.c_void_p, _u8p, ctypes.c_uint32]),
+    # gnark point arrays (key files)
+    "zklc_bn254_g1_decode_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    "zklc_bn254_g2_decode_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    "zklc_bn254_g1_decode_host": (ctypes.c_int32, [_u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    "zklc_bn254_g2_decode_host": (ctypes.c_int32, [_u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     "zklc_bn254_fr_ntt": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
@@ -139,6 +144,9 @@ _SIGS = {
 }
 
 NTT_INVERSE, NTT_IN_BITREV, NTT_OUT_BITREV = 1, 2, 4
+POINT_OK, POINT_INFINITY, POINT_BAD_ENCODING, POINT_NOT_ON_CURVE, POINT_NOT_IN_SUBGROUP = range(5)
+POINTS_COMPRESSED, POINTS_CHECK_SUBGROUP = 1, 2
+POINT_CLASS_NAMES = ("OK", "INFINITY", "BAD_ENCODING", "NOT_ON_CURVE", "NOT_IN_SUBGROUP")
 
 _lib = None
 

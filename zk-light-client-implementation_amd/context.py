@@ -270,6 +270,14 @@ class Context:
                                                        gt.ctypes.data if want_gt else None))
         return ok, gt
 
+    def bn254_points_decode_dev(self, d_bytes, n, d_words, d_status, d_summary, group=1, flags=0, stream=None):
+        """n points of a gnark key file's point array (d_bytes: the file's bytes in HBM, 16-byte aligned; flags: _lib.POINTS_*) ->
+        d_words int64 / uint64 [n, 8] (group=2: [n, 16]) in the layout the multi-exponentiations read, d_status uint32 [n]
+        (_lib.POINT_*), d_summary 4 x u64: OK, infinity, rejected, index of the first rejected point.  Enqueue only."""
+        fn = self._lib.zklc_bn254_g1_decode_dev if group == 1 else self._lib.zklc_bn254_g2_decode_dev
+        self._check(fn(self._h, _stream_ptr(stream), _dev_ptr(d_bytes), n, flags, _dev_ptr(d_words), _dev_ptr(d_status),
+                       _dev_ptr(d_summary)))
+
     def bn254_fr_ntt(self, data, flags=0, coset=0):
         """data: uint64 [n, 4] Fr elements in gnark Montgomery layout -> transformed copy"""
         a = np.ascontiguousarray(data, dtype=np.uint64).reshape(-1, 4).copy()

@@ -57,6 +57,25 @@ static void g16_build_rows(const fp &x, const fp &y, g16_tab_entry *out) {
     }
 }
 
+// constants of the twist equation and of the Fp2 square root, from the field code itself
+const g16_key &g16_key_constants() {
+    static const g16_key key = [] {
+        g16_key k;
+        memset(&k, 0, sizeof(k));
+        const u32 nine[8] = {9, 0, 0, 0, 0, 0, 0, 0}, two[8] = {2, 0, 0, 0, 0, 0, 0, 0};
+        const fp three = FP_THREE, one = FP_ONE;
+        fp2 xi, t3;
+        xi.c0 = g16_fp_from_words(nine);
+        xi.c1 = one;
+        t3.c0 = three;
+        t3.c1 = fp_zero();
+        k.twist_b = fp2_reduce(fp2_mul(t3, fp2_inv(xi)));
+        k.half = fp_inv(g16_fp_from_words(two));
+        return k;
+    }();
+    return key;
+}
+
 extern "C" int32_t zklc_groth16_verifier_create(zklc_ctx *, const uint64_t *alpha1, const uint64_t *beta2, const uint64_t *gamma2,
                                                 const uint64_t *delta2, const uint64_t *K, uint32_t n_public,
                                                 zklc_groth16_verifier **out) {
@@ -67,18 +86,8 @@ extern "C" int32_t zklc_groth16_verifier_create(zklc_ctx *, const uint64_t *alph
     zklc_groth16_verifier *v = new (std::nothrow) zklc_groth16_verifier();
     if (!v) return ZKLC_ERR_OOM;
     g16_key &k = v->key;
-    memset(&k, 0, sizeof(k));
+    k = g16_key_constants();
     k.n_public = n_public;
-    // constants of the twist equation and of the Fp2 square root, from the field code itself
-    const u32 nine[8] = {9, 0, 0, 0, 0, 0, 0, 0}, two[8] = {2, 0, 0, 0, 0, 0, 0, 0};
-    const fp three = FP_THREE, one = FP_ONE;
-    fp2 xi, t3;
-    xi.c0 = g16_fp_from_words(nine);
-    xi.c1 = one;
-    t3.c0 = three;
-    t3.c1 = fp_zero();
-    k.twist_b = fp2_reduce(fp2_mul(t3, fp2_inv(xi)));
-    k.half = fp_inv(g16_fp_from_words(two));
     bool ok = true, inf = false;
     fp ax, ay;
     ok = g16_read_g1(alpha1, ax, ay, inf) && !inf;

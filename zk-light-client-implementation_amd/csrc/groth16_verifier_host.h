@@ -26,3 +26,6 @@ struct zklc_groth16_verifier {
 
 // a * b without wrapping; false when the product does not fit
 inline bool g16_mul_ok(uint64_t a, uint64_t b, uint64_t *out) { return !__builtin_mul_overflow(a, b, out); }
+// a key that holds only the constants of the twist equation and of the Fp2 square root: twist_b = 3 / (9 + u), half = 1 / 2, the
+// rest zero (groth16_verifier_host.cpp: host code, computed once with the field functions)
+const g16_key &g16_key_constants();

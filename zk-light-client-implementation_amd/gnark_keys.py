@@ -11,6 +11,10 @@ eight words Verifier.sol consumes (tests/test_formats.py).  The rest -- field or
 the domain header -- is restated from the published marshal code; everything after the last field this module understands
 (Pedersen commitment keys: the reference's circuit has none, Verifier.sol carries no commitment terms) is kept as an opaque
 trailer and reported, not interpreted.  Tests: round trips and structure only (tests/test_gnark_keys.py).
+
+`load_pk` (end of this module) reads the same layout with the point arrays decoded and validated by the library -- one lane per
+point on the GPU, or the same lane functions on host threads (include/zklc.h zklc_bn254_g{1,2}_decode_{dev,host}) -- so that the
+reader is not the bottleneck of a start-up; it pins nothing: read_g1 / read_g2 below stay the specification of those kernels.
 """
 import struct
 
@@ -25,8 +29,9 @@ _HALF_P = (P - 1) // 2
 
 
 class _Reader:
-    def __init__(self, data):
-        self.b, self.o = memoryview(bytes(data)), 0
+    def __init__(self, data, copy=True):
+        # copy=False: a view of the caller's buffer (a memory-mapped key file: load_pk)
+        self.b, self.o = memoryview(bytes(data) if copy else data), 0
 
     def take(self, n):
         if self.o + n > len(self.b):
@@ -266,10 +271,8 @@ def pk_to_gnark_bytes(pk, raw=True, trailer=b""):
     return b"".join(out)
 
 
-def pk_from_gnark_bytes(data, n_public, raw=True):
-    """-> the dict `Groth16Prover` takes (compacted A / B1 / B2 + infinity masks).  n_public: public inputs WITHOUT the constant
-    wire (gnark keeps it in the R1CS file, not in the key: len(K) = nbWires - nbPublic where nbPublic counts the constant one)."""
-    rd = _Reader(data)
+def _read_domain(rd):
+    """the fft.Domain header -> the domain size"""
     n = rd.u64()
     if n == 0 or n & (n - 1):
         raise ProofInvalid("domain size is not a power of two")
@@ -277,6 +280,33 @@ def pk_from_gnark_bytes(data, n_public, raw=True):
     rd.fr(), rd.fr(), rd.fr()
     if card_inv * n % R != 1 or pow(gen, n, R) != 1 or (n > 1 and pow(gen, n // 2, R) == 1):
         raise ProofInvalid("domain header inconsistent")
+    return n
+
+
+def _read_tail(rd, lens, n, n_public):
+    """what follows B2: wire counts, infinity masks, trailer, checked against the lengths of the five point arrays
+    -> (infinity_a, infinity_b, trailer)"""
+    n_wires, n_inf_a, n_inf_b = rd.u64(), rd.u64(), rd.u64()
+    if n_wires > (1 << 32):
+        raise ProofInvalid("wire count implausible")
+    inf_a = np.frombuffer(rd.take(n_wires), dtype=np.uint8).astype(bool)
+    inf_b = np.frombuffer(rd.take(n_wires), dtype=np.uint8).astype(bool)
+    if int(inf_a.sum()) != n_inf_a or int(inf_b.sum()) != n_inf_b:
+        raise ProofInvalid("infinity masks do not match their counts")
+    if lens["A"] != n_wires - n_inf_a or lens["B1"] != n_wires - n_inf_b or lens["B2"] != n_wires - n_inf_b:
+        raise ProofInvalid("point arrays do not match the infinity masks")
+    if lens["Z"] != n - 1 and lens["Z"] != n:
+        raise ProofInvalid("Z has %d points for a domain of %d" % (lens["Z"], n))
+    if lens["K"] != n_wires - 1 - int(n_public):
+        raise ProofInvalid("K has %d points, expected nbWires - nbPublic = %d" % (lens["K"], n_wires - 1 - int(n_public)))
+    return inf_a, inf_b, bytes(rd.b[rd.o:])
+
+
+def pk_from_gnark_bytes(data, n_public, raw=True):
+    """-> the dict `Groth16Prover` takes (compacted A / B1 / B2 + infinity masks).  n_public: public inputs WITHOUT the constant
+    wire (gnark keeps it in the R1CS file, not in the key: len(K) = nbWires - nbPublic where nbPublic counts the constant one)."""
+    rd = _Reader(data)
+    n = _read_domain(rd)
     g1, g2, pad1, pad2 = _padded(rd, raw)
     pk = {"n": n, "n_public": int(n_public), "alpha1": g1(), "beta1": g1(), "delta1": g1()}
     pk["A"] = _read_points(rd, read_g1, pad1)
@@ -285,22 +315,8 @@ def pk_from_gnark_bytes(data, n_public, raw=True):
     pk["K"] = _read_points(rd, read_g1, pad1)
     pk["beta2"], pk["delta2"] = g2(), g2()
     pk["B2"] = _read_points(rd, read_g2, pad2)
-    n_wires, n_inf_a, n_inf_b = rd.u64(), rd.u64(), rd.u64()
-    if n_wires > (1 << 32):
-        raise ProofInvalid("wire count implausible")
-    inf_a = np.frombuffer(rd.take(n_wires), dtype=np.uint8).astype(bool)
-    inf_b = np.frombuffer(rd.take(n_wires), dtype=np.uint8).astype(bool)
-    if int(inf_a.sum()) != n_inf_a or int(inf_b.sum()) != n_inf_b:
-        raise ProofInvalid("infinity masks do not match their counts")
-    if len(pk["A"]) != n_wires - n_inf_a or len(pk["B1"]) != n_wires - n_inf_b or len(pk["B2"]) != n_wires - n_inf_b:
-        raise ProofInvalid("point arrays do not match the infinity masks")
-    if len(pk["Z"]) != n - 1 and len(pk["Z"]) != n:
-        raise ProofInvalid("Z has %d points for a domain of %d" % (len(pk["Z"]), n))
+    pk["infinity_a"], pk["infinity_b"], pk["trailer"] = _read_tail(rd, {k: len(pk[k]) for k in ("A", "B1", "Z", "K", "B2")}, n, n_public)
     pk["Z"] = pk["Z"][:n - 1]
-    if len(pk["K"]) != n_wires - 1 - int(n_public):
-        raise ProofInvalid("K has %d points, expected nbWires - nbPublic = %d" % (len(pk["K"]), n_wires - 1 - int(n_public)))
-    pk["infinity_a"], pk["infinity_b"] = inf_a, inf_b
-    pk["trailer"] = bytes(rd.b[rd.o:])
     return pk
 
 
@@ -314,3 +330,142 @@ def points_to_words(pts, g2=False):
         coords = (p[0][0], p[0][1], p[1][0], p[1][1]) if g2 else p
         out[i] = np.array([v for c in coords for v in fp_to_mont_words(c)], dtype=np.uint64)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- batched decoding (C ABI)
+# include/zklc.h zklc_bn254_g{1,2}_decode_{dev,host}: the point arrays of a key file go through the library -- one lane per point
+# on the GPU, or the same lane functions on host threads -- instead of through read_g1 / read_g2 above, which stay the specification
+# (and the fallback for a file that mixes encodings).
+DECODE_WORKGROUP = 256          # lanes per workgroup of the kernels (csrc/gnark_points.hip)
+_CHUNK_POINTS = 1 << 20
+
+
+def _aligned_u8(nbytes):
+    """zeroed uint8 array whose address is a multiple of 64"""
+    raw = np.zeros(nbytes + 64, dtype=np.uint8)
+    off = (-raw.ctypes.data) % 64
+    return raw[off:off + nbytes]
+
+
+def _stride(g2, compressed):
+    return (128 if g2 else 64) >> (1 if compressed else 0)
+
+
+def decode_points_host(data, n, g2=False, compressed=False, check_subgroup=False, nthreads=0, chunk_points=_CHUNK_POINTS):
+    """n fixed-stride points of a gnark point array (any buffer of uint8) on host threads (0 = 16), no GPU
+    -> (words uint64 [n, 8 | 16], status uint32 [n], summary [OK, infinity, rejected, first rejected index | None])"""
+    from . import _lib
+    lib = _lib.load()
+    fn = lib.zklc_bn254_g2_decode_host if g2 else lib.zklc_bn254_g1_decode_host
+    flags = (_lib.POINTS_COMPRESSED if compressed else 0) | (_lib.POINTS_CHECK_SUBGROUP if check_subgroup else 0)
+    stride, width = _stride(g2, compressed), 16 if g2 else 8
+    src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1)
+    if src.size < n * stride:
+        raise ValueError("point array buffer too small")
+    words = _aligned_u8(n * width * 8).view(np.uint64).reshape(n, width)
+    status = np.zeros(n, dtype=np.uint32)
+    total, summary = [0, 0, 0, None], np.zeros(4, dtype=np.uint64)
+    stage = _aligned_u8(min(max(n, 1), chunk_points) * stride)
+    for off in range(0, max(n, 1), chunk_points):
+        k = min(chunk_points, n - off)
+        stage[:k * stride] = src[off * stride:(off + k) * stride]        # the file's bytes to an aligned address, nothing else
+        rc = fn(stage.ctypes.data, k, flags, nthreads, words.ctypes.data + off * width * 8, status.ctypes.data + off * 4,
+                summary.ctypes.data)
+        if rc != 0:
+            raise _lib.ZklcError(rc)
+        _add_summary(total, summary, off)
+    return words, status, total
+
+
+def _add_summary(total, summary, off):
+    for j in range(3):
+        total[j] += int(summary[j])
+    if total[3] is None and int(summary[3]) != (1 << 64) - 1:
+        total[3] = off + int(summary[3])
+
+
+def decode_points_dev(ctx, data, n, g2=False, compressed=False, check_subgroup=False, chunk_points=_CHUNK_POINTS):
+    """the same on ctx's GPU: the bytes are uploaded chunk by chunk through one page-locked buffer and decoded there
+    -> (words: torch int64 [n, 8 | 16] on the device, status: torch int32 [n] on the device, summary as decode_points_host)"""
+    import torch
+    from . import _lib
+    flags = (_lib.POINTS_COMPRESSED if compressed else 0) | (_lib.POINTS_CHECK_SUBGROUP if check_subgroup else 0)
+    stride, width = _stride(g2, compressed), 16 if g2 else 8
+    src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1)
+    if src.size < n * stride:
+        raise ValueError("point array buffer too small")
+    dev = torch.device("cuda", ctx.device_id)
+    words = torch.zeros((n, width), dtype=torch.int64, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_summary = torch.zeros(4, dtype=torch.int64, device=dev)
+    cap = min(max(n, 1), chunk_points)
+    stage = torch.empty(cap * stride, dtype=torch.uint8).pin_memory()
+    d_bytes = torch.empty(cap * stride, dtype=torch.uint8, device=dev)
+    total = [0, 0, 0, None]
+    for off in range(0, max(n, 1), chunk_points):
+        k = min(chunk_points, n - off)
+        stage.numpy()[:k * stride] = src[off * stride:(off + k) * stride]
+        d_bytes[:k * stride].copy_(stage[:k * stride])
+        torch.cuda.current_stream(dev).synchronize()               # torch copies on ITS stream; the kernels run on the context's
+        ctx.bn254_points_decode_dev(d_bytes, k, words.data_ptr() + off * width * 8, status.data_ptr() + off * 4, d_summary,
+                                    group=2 if g2 else 1, flags=flags, stream=ctx.stream_ptr())
+        ctx.synchronize()
+        _add_summary(total, d_summary.cpu().numpy().view(np.uint64), off)
+    return words, status, total
+
+
+def _span(rd, stride, unit):
+    """a point array's length prefix and extent -> (offset, count); the reader moves past it"""
+    count = rd.u32()
+    left = len(rd.b) - rd.o
+    if count * stride > left:
+        # where the point-by-point reader runs out: it takes `unit` bytes at a time
+        raise ProofInvalid("key file truncated at byte %d (+%d)" % (rd.o + left // unit * unit, unit))
+    start = rd.o
+    rd.o += count * stride
+    return start, count
+
+
+def load_pk(src, n_public, raw=True, ctx=None, check_subgroup=True, nthreads=0, chunk_points=_CHUNK_POINTS):
+    """pk.bin -> the dict `Groth16Prover` takes, the five point arrays decoded and validated by the library.  src: a path (mapped
+    with np.memmap: a multi-gigabyte file never becomes Python objects) or a buffer.  Parses what pk_from_gnark_bytes parses, with
+    the same checks and messages.  ctx=None: host threads, arrays as uint64 numpy under A_words, B1_words, Z_words, K_words,
+    B2_words; with a Context: on its GPU, arrays as device tensors under A_dev ... B2_dev.  B2 is tested for membership in the
+    r-torsion subgroup unless check_subgroup=False.  A rejected point raises ProofInvalid with the array, the index and the class."""
+    import os
+    from . import _lib
+    if isinstance(src, (str, os.PathLike)):
+        buf = np.memmap(src, dtype=np.uint8, mode="r")
+    else:
+        buf = np.frombuffer(src, dtype=np.uint8)
+    rd = _Reader(buf, copy=False)
+    n = _read_domain(rd)
+    g1, g2, _, _ = _padded(rd, raw)
+    pk = {"n": n, "n_public": int(n_public), "alpha1": g1(), "beta1": g1(), "delta1": g1()}
+    s1, s2 = _stride(False, not raw), _stride(True, not raw)
+    spans = {name: _span(rd, s1, 32) for name in ("A", "B1", "Z", "K")}
+    pk["beta2"], pk["delta2"] = g2(), g2()
+    spans["B2"] = _span(rd, s2, 64)
+    pk["infinity_a"], pk["infinity_b"], pk["trailer"] = _read_tail(rd, {k: v[1] for k, v in spans.items()}, n, n_public)
+    for name, (start, count) in spans.items():
+        is_g2 = name == "B2"
+        stride = s2 if is_g2 else s1
+        data = buf[start:start + count * stride]
+        kw = dict(g2=is_g2, compressed=not raw, check_subgroup=check_subgroup and is_g2, chunk_points=chunk_points)
+        if ctx is None:
+            words, status, summary = decode_points_host(data, count, nthreads=nthreads, **kw)
+        else:
+            words, status, summary = decode_points_dev(ctx, data, count, **kw)
+        if summary[3] is not None:
+            i = summary[3]
+            cls = int(status[i])
+            msg = "%s[%d]: %s" % (name, i, _lib.POINT_CLASS_NAMES[cls])
+            flag = int(buf[start + i * stride]) >> 6
+            if cls == _lib.POINT_BAD_ENCODING and (flag in (2, 3) if raw else flag == 0):
+                msg += (": a flag of the other encoding -- the file mixes point encodings; the point-by-point Python reader "
+                        "(pk_from_gnark_bytes) is the fallback")
+            raise ProofInvalid(msg)
+        if name == "Z":
+            words = words[:n - 1]
+        pk[name + ("_words" if ctx is None else "_dev")] = words
+    return pk

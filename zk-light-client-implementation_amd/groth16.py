@@ -61,7 +61,8 @@ def g2_words(pt):
 class Groth16Prover:
     """One proving key resident on one GPU.  pk: dict with n (domain size), n_public, point lists A, B1, K, Z (G1), B2 (G2) and
     alpha1, beta1, delta1 (G1), beta2, delta2 (G2) as affine integer tuples (None = infinity) or as uint64 arrays in gnark's
-    layout under the same keys with the suffix `_words`."""
+    layout under the same keys with the suffix `_words`; the five point lists also as int64 device tensors of that layout with
+    the suffix `_dev` (gnark_keys.load_pk: decoded and validated on the GPU, they never visit the host)."""
 
     def __init__(self, ctx, pk):
         import torch
@@ -72,6 +73,10 @@ class Groth16Prover:
         assert 1 << self.log_n == self.n
 
         def pts(name, conv, width):
+            if name + "_dev" in pk:                               # already in HBM (gnark_keys.load_pk with a context)
+                t = pk[name + "_dev"]
+                assert t.device == self.dev and t.dtype == torch.int64 and t.is_contiguous() and t.shape[-1] == width
+                return t.reshape(-1, width)
             if name + "_words" in pk:
                 a = np.ascontiguousarray(pk[name + "_words"], dtype=np.uint64).reshape(-1, width)
             else:
@@ -103,8 +108,10 @@ class Groth16Prover:
         # per operand no longer sit in the 256 MB last-level cache the way 2^22 plain 64-byte records do.  Default: plain.
         self.fixed = os.environ.get("ZKLC_GROTH16_FIXED", "0") == "1"
         self.n_priv = K.shape[0]
-        ops = {"A": (np.concatenate([A, al, de1]), 1), "B1": (np.concatenate([B1, be1, de1]), 1),
-               "B2": (np.concatenate([B2, be2, de2]), 2), "K": (K, 1), "Z": (Z, 1)}
+        # an array that is a device tensor is joined with alpha / beta / delta on the device: no host copy of it
+        cat = lambda parts: (torch.cat([x if torch.is_tensor(x) else up(x) for x in parts]) if torch.is_tensor(parts[0])
+                             else np.concatenate(parts))
+        ops = {"A": (cat([A, al, de1]), 1), "B1": (cat([B1, be1, de1]), 1), "B2": (cat([B2, be2, de2]), 2), "K": (K, 1), "Z": (Z, 1)}
         self.delta1_words = de1.reshape(8).copy()
         self.n_op = {k: v[0].shape[0] for k, v in ops.items()}
         self.d_op = {}
@@ -112,7 +119,7 @@ class Groth16Prover:
             if arr.shape[0] == 0:                                 # no private wire: the K sum is skipped
                 self.d_op[name] = None
                 continue
-            d_pts = up(arr)
+            d_pts = arr if torch.is_tensor(arr) else up(arr)
             if self.fixed:
                 self.d_op[name] = ctx.bn254_msm_fixed_table(d_pts, arr.shape[0], group, stream=ctx.stream_ptr())
                 ctx.synchronize()                                 # d_pts goes back to torch's allocator below
