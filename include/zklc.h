@@ -518,6 +518,43 @@ int32_t zklc_bn254_fr_ntt_dev(zklc_ctx *ctx, void *stream, uint64_t *d_data, uin
 int32_t zklc_bn254_fr_mul_sub_scale_dev(zklc_ctx *ctx, void *stream, uint64_t *d_a, const uint64_t *d_b, const uint64_t *d_c,
                                         const uint64_t *scale, uint64_t n);
 
+/* The constraint system of `groth16.Prove(r1cs, pk, witness)` (gnark-plonky2-verifier/cmd/web-api.go:77), resident beside the
+ * proving key: a = A w, b = B w, c = C w per constraint from the solved witness, straight into the buffers the transforms of
+ * `computeH` take, and the test a_j b_j = c_j.  Replaces what gnark's solver leaves behind for the prover (`solution.a / b / c` of
+ * constraint/bn254/solver.go, un-vendored) and its error "constraint #j is not satisfied"; SOLVING the system from the public
+ * inputs (gnark's hints) and reading `r1cs.bin` stay the caller's.
+ * The three matrices arrive as ONE CSR of 3 n_constraints rows: row m n_constraints + j is row j of matrix m (A, B, C = 0, 1, 2).
+ * row_ptr: 3 n_constraints + 1 u64; term_wire / term_coeff: nnz u32 each, the wire and the index into coeffs; coeffs: n_coeff x 4
+ * u64, gnark-crypto's memory layout (x 2^256 mod r).  No id of the dictionary has a reserved meaning.  Everything is validated
+ * once, here, on the host, before anything is indexed: n_constraints <= 2^30, 1 <= n_wires <= 2^32, nnz <= 2^40, n_coeff <= 2^30
+ * (sizes are compared against these bounds, never multiplied first), row_ptr[0] = 0, row_ptr non-decreasing, its last entry = nnz,
+ * every wire < n_wires, every coefficient id < n_coeff, every coefficient < r; ZKLC_ERR_INVALID_ARG otherwise.  The arrays are
+ * copied (the caller's may go); built here: the class of every dictionary entry (0, +1, -1, general) packed into the terms, and
+ * the rows binned by length for groups of 1 / 8 / 64 lanes.  ctx may be NULL (host only: zklc_r1cs_abc_host); with a context the
+ * system is uploaded to that context's GPU and zklc_r1cs_abc_dev takes contexts of that GPU. */
+typedef struct zklc_r1cs zklc_r1cs;
+#define ZKLC_R1CS_CHECK 1u /* flags: also test a_j b_j = c_j for j < n_constraints and fill the summary */
+int32_t zklc_r1cs_create(zklc_ctx *ctx, uint64_t n_constraints, uint64_t n_wires, const uint64_t *row_ptr, const uint32_t *term_wire,
+                         const uint32_t *term_coeff, uint64_t nnz, const uint64_t *coeffs, uint32_t n_coeff, zklc_r1cs **out);
+void zklc_r1cs_destroy(zklc_r1cs *s);
+/* bytes of device workspace one evaluation needs (the witness in Montgomery form: n_wires x 32) */
+uint64_t zklc_r1cs_workspace_bytes(const zklc_r1cs *s);
+/* d_witness_regular: n_wires x 4 u64, REGULAR form, the array the multi-exponentiations read as scalars (a word >= r is reduced, as
+ * they do); n: the domain size, n_constraints <= n <= 2^30.  d_a, d_b, d_c: n x 4 u64 each, written in full: every element
+ * canonical (< r) in gnark-crypto's Montgomery form, rows n_constraints .. n - 1 zero (the buffers need not be clear).  With
+ * ZKLC_R1CS_CHECK d_summary (2 u64) receives the number of constraints with a_j b_j != c_j and the index of the first one
+ * (all-ones: none); an unsatisfied system is a summary, not an error of the call.  Enqueue only: nothing is read back, the caller
+ * reads the summary after the stream.  ZKLC_ERR_INVALID_ARG for n < n_constraints, a missing pointer, a witness / output /
+ * workspace pointer not 16-byte aligned (summary: 8), unknown flag bits, ZKLC_R1CS_CHECK without d_summary, workspace_bytes below
+ * zklc_r1cs_workspace_bytes, or a system created without a context / on another GPU. */
+int32_t zklc_r1cs_abc_dev(zklc_ctx *ctx, void *stream, const zklc_r1cs *s, const uint64_t *d_witness_regular, uint64_t n,
+                          uint64_t *d_a, uint64_t *d_b, uint64_t *d_c, uint32_t flags, uint64_t *d_summary, void *d_workspace,
+                          uint64_t workspace_bytes);
+/* the same on the host only (the same lane functions compiled for the host), 256 rows per task on up to nthreads threads (0 = 16):
+ * host pointers with the same alignment rule, no GPU and no context needed; bit for bit the words and the summary of the kernels */
+int32_t zklc_r1cs_abc_host(const zklc_r1cs *s, const uint64_t *witness_regular, uint64_t n, uint64_t *a, uint64_t *b, uint64_t *c,
+                           uint32_t flags, uint32_t nthreads, uint64_t *summary);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,15 @@ _SIGS = {
     "zklc_bn254_g2_decode_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     "zklc_bn254_g1_decode_host": (ctypes.c_int32, [_u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     "zklc_bn254_g2_decode_host": (ctypes.c_int32, [_u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    # constraint system (A w, B w, C w)
+    "zklc_r1cs_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, _u8p, _u8p, _u8p, ctypes.c_uint64, _u8p,
+                                          ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
+    "zklc_r1cs_destroy": (None, [ctypes.c_void_p]),
+    "zklc_r1cs_workspace_bytes": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "zklc_r1cs_abc_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p,
+                                           ctypes.c_uint32, _u8p, _u8p, ctypes.c_uint64]),
+    "zklc_r1cs_abc_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32,
+                                            _u8p]),
     "zklc_bn254_fr_ntt": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,

@@ -3,7 +3,10 @@
 Reference: gnark-plonky2-verifier/cmd/web-api.go:77 (`groth16.Prove(r1cs, pk, witness)`), :84 (`groth16.Verify`), :90-98 (the 256
 proof bytes); gnark v0.9.1 backend/groth16/bn254/prove.go is un-vendored (go.mod:8).  What it computes, and what runs where:
 
-  host    a, b, c = (A w, B w, C w) per constraint (the solved witness is the caller's: gnark's solver is the Go side)
+  host    the solved witness (gnark's solver and its hints are the Go side)
+  GPU     a, b, c = (A w, B w, C w) per constraint and the test a_j b_j = c_j: `prove_witness` with a resident constraint system
+          (zklc_amd/r1cs.py, zklc_r1cs_abc_dev: rows binned by length, 1 / 8 / 64 lanes per row), on stream 3 in front of computeH,
+          reading the witness the sums have uploaded.  `prove` / `prove_words` take a, b, c from the caller instead (host).
   GPU     computeH: 3 inverse NTTs, 3 coset NTTs, (a b - c) / (5^n - 1) pointwise, 1 coset inverse NTT  (zklc_bn254_fr_ntt_dev,
           zklc_bn254_fr_mul_sub_scale_dev) -- data stays in HBM between the seven transforms
   GPU     Ar  = alpha + sum_i w_i A_i + r delta                       one G1 MSM (alpha, delta among the bases)        stream 1
@@ -19,6 +22,8 @@ resident on the device.  No CPU fallback: every transform and MSM is a kernel la
 import os
 
 import numpy as np
+
+from .r1cs import UnsatisfiedConstraint, summary_tuple  # noqa: F401  (UnsatisfiedConstraint: raised by prove_witness)
 
 R = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
 P = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47
@@ -62,9 +67,11 @@ class Groth16Prover:
     """One proving key resident on one GPU.  pk: dict with n (domain size), n_public, point lists A, B1, K, Z (G1), B2 (G2) and
     alpha1, beta1, delta1 (G1), beta2, delta2 (G2) as affine integer tuples (None = infinity) or as uint64 arrays in gnark's
     layout under the same keys with the suffix `_words`; the five point lists also as int64 device tensors of that layout with
-    the suffix `_dev` (gnark_keys.load_pk: decoded and validated on the GPU, they never visit the host)."""
+    the suffix `_dev` (gnark_keys.load_pk: decoded and validated on the GPU, they never visit the host).
+    r1cs (optional): the key's constraint system as a zklc_amd.r1cs.R1CS created with a Context of the same GPU -- with it
+    `prove_witness` / `prove_witness_words` go from the solved witness to the proof; the prover does not own it (close it yourself)."""
 
-    def __init__(self, ctx, pk):
+    def __init__(self, ctx, pk, r1cs=None):
         import torch
         self.ctx, self.torch = ctx, torch
         self.dev = torch.device("cuda", ctx.device_id)
@@ -146,6 +153,13 @@ class Groth16Prover:
         from .context import Context
         self.ctx2 = Context(ctx.device_id)
         self.ctx3 = Context(ctx.device_id)           # (the device's high priority for this stream: measured, no effect -- profiles/r06z2_*)
+        self.r1cs = r1cs
+        if r1cs is not None:
+            if r1cs.n_wires != self.n_wires or r1cs.n_constraints > self.n:
+                raise ValueError("groth16: the constraint system (%d wires, %d constraints) does not fit the key (%d wires, domain %d)"
+                                 % (r1cs.n_wires, r1cs.n_constraints, self.n_wires, self.n))
+            if r1cs.ctx is None or r1cs.ctx.device_id != ctx.device_id:
+                raise ValueError("groth16: the constraint system is not resident on the prover's GPU")
         torch.cuda.synchronize(self.dev)
         self.last_ms = {}
 
@@ -217,6 +231,38 @@ class Groth16Prover:
         """the same with the operands as arrays, the way a cgo shim hands them over: w_reg uint64 [n_wires, 4] = the witness in
         regular (non-Montgomery) form (gnark converts with `fr.Element.BigInt` before MultiExp as well), abc_mont three uint64
         [n, 4] arrays in gnark's Montgomery layout"""
+        return self._prove_words(w_reg, abc_mont, r, s, False)
+
+    def prove_witness(self, witness, r, s, check=True):
+        """`groth16.Prove(r1cs, pk, witness)` from the solved witness alone (the prover was given the constraint system): witness =
+        all wire values (ints, witness[0] = 1), r, s = the blinding scalars.  A w, B w, C w are evaluated on the GPU.  check=True:
+        a witness that does not satisfy the system raises UnsatisfiedConstraint(index of the first violated constraint, count) and
+        no proof is returned; check=False proves whatever it is given, as `prove` does.  Returns the 8 integers of `prove`."""
+        assert len(witness) == self.n_wires and witness[0] % R == 1
+        return self.prove_witness_words(np.array([fr_to_regular_words(x) for x in witness], dtype=np.uint64), r, s, check)
+
+    def prove_witness_words(self, w_reg, r, s, check=True):
+        """the same with the witness as uint64 [n_wires, 4] in regular form: the only operand that crosses PCIe"""
+        if self.r1cs is None:
+            raise ValueError("groth16: prove_witness needs the constraint system (Groth16Prover(ctx, pk, r1cs))")
+        return self._prove_words(w_reg, None, r, s, check)
+
+    def _sync_all(self):
+        """wait for the three streams, each even if another one's wait fails; the first failure is raised afterwards"""
+        err = None
+        for c in (self.ctx, self.ctx2, self.ctx3):
+            try:
+                c.synchronize()
+            except Exception as e:  # noqa: BLE001
+                err = err or e
+        if err is not None:
+            raise err
+
+    def _prove_words(self, w_reg, abc_mont, r, s, check):
+        """abc_mont given: the caller's a, b, c are uploaded (prove_words); None: the resident constraint system evaluates them on
+        ctx3's stream from the uploaded witness (prove_witness_words).  Once the first sum is enqueued, nothing leaves this method
+        -- result or exception -- before all three streams are idle: their kernels read and write tensors that go back to torch's
+        allocator when the frame is left."""
         import time
         torch = self.torch
         t0 = time.perf_counter()
@@ -234,36 +280,57 @@ class Groth16Prover:
         infs = {k: torch.ones(1, dtype=torch.int32, device=self.dev) for k in outs}      # 1 = infinity until a sum has run
         tsync()
         t1 = time.perf_counter()
-        # stream 2: Bs = beta + sum_i w_i B_i + s delta (G2);  stream 1: Ar, then Bs1, then the K part of Krs
-        self._msm(self.ctx2, "B2", sc_b, outs["B2"], infs["B2"], self.ws2, group=2)
-        self._msm(self.ctx, "A", sc_a, outs["A"], infs["A"], self.ws1)
-        self._msm(self.ctx, "B1", sc_b, outs["B1"], infs["B1"], self.ws1)
-        if self.n_priv:
-            self._msm(self.ctx, "K", sc_kp, outs["K"], infs["K"], self.ws1)
-        # stream 3: computeH (the three operands cross PCIe while the sums above run), then the Z part of Krs straight from h
-        d = [up(x) for x in abc_mont]
-        tsync()
-        self._compute_h_enqueue(d, self.ctx3)
-        t2 = time.perf_counter()
-        self._msm(self.ctx3, "Z", d[0], outs["Z"], infs["Z"], self.ws3)        # the first n - 1 coefficients of h
-        self.ctx.synchronize()
-        self.ctx3.synchronize()
-        if int(infs["A"][0]) or int(infs["B1"][0]):
-            raise ValueError("groth16: a proof element is the point at infinity (degenerate key or witness)")
-        # Krs = sum_priv w_i K_i + sum_j h_j Z_j + s Ar + r Bs1 - r s delta1: five points, through the same kernels
-        h = lambda t: t.cpu().numpy().view(np.uint64)
-        part = lambda k: np.zeros(8, np.uint64) if int(infs[k][0]) else h(outs[k])
-        pts5 = np.stack([part("K"), part("Z"), h(outs["A"]), h(outs["B1"]), self.delta1_words])
-        k_w, k_inf = self.ctx.bn254_g1_msm(pts5, tail(1, 1, s, r, (R - r * s % R) % R))
-        self.ctx2.synchronize()
-        t3 = time.perf_counter()
-        if k_inf or int(infs["B2"][0]):
-            raise ValueError("groth16: a proof element is the point at infinity (degenerate key or witness)")
-        a_w, b_w = h(outs["A"]), h(outs["B2"])
-        f = fp_from_mont_words
-        proof = [f(a_w[0:4]), f(a_w[4:8]), f(b_w[4:8]), f(b_w[0:4]), f(b_w[12:16]), f(b_w[8:12]), f(k_w[0:4]), f(k_w[4:8])]
-        self.last_ms = {"witness_upload_and_scalars": (t1 - t0) * 1e3, "operands_of_compute_h_cross_pcie_beside_A_B1_K_B2": (t2 - t1) * 1e3,
-                        "compute_h_z_and_tails": (t3 - t2) * 1e3, "total": (t3 - t0) * 1e3, "fixed_base": self.fixed}
+        try:
+            # stream 2: Bs = beta + sum_i w_i B_i + s delta (G2);  stream 1: Ar, then Bs1, then the K part of Krs
+            self._msm(self.ctx2, "B2", sc_b, outs["B2"], infs["B2"], self.ws2, group=2)
+            self._msm(self.ctx, "A", sc_a, outs["A"], infs["A"], self.ws1)
+            self._msm(self.ctx, "B1", sc_b, outs["B1"], infs["B1"], self.ws1)
+            if self.n_priv:
+                self._msm(self.ctx, "K", sc_kp, outs["K"], infs["K"], self.ws1)
+            # stream 3: computeH (the three operands cross PCIe while the sums above run), then the Z part of Krs straight from h
+            ev = d_sum = None
+            if abc_mont is not None:
+                d = [up(x) for x in abc_mont]
+                tsync()
+            else:
+                d = [torch.empty((self.n, 4), dtype=torch.int64, device=self.dev) for _ in range(3)]
+                d_sum = torch.empty(2, dtype=torch.int64, device=self.dev) if check else None
+                s3 = torch.cuda.ExternalStream(self.ctx3.stream_ptr(), device=self.dev)
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                tsync()
+                ev[0].record(s3)
+                self.r1cs.enqueue(self.ctx3, d_w, self.n, d[0], d[1], d[2], d_sum)
+                ev[1].record(s3)
+            self._compute_h_enqueue(d, self.ctx3)
+            t2 = time.perf_counter()
+            self._msm(self.ctx3, "Z", d[0], outs["Z"], infs["Z"], self.ws3)        # the first n - 1 coefficients of h
+            self.ctx.synchronize()
+            self.ctx3.synchronize()
+            if d_sum is not None:
+                count, first = summary_tuple(d_sum.cpu().numpy().view(np.uint64))
+                if count:
+                    raise UnsatisfiedConstraint(first, count)
+            if int(infs["A"][0]) or int(infs["B1"][0]):
+                raise ValueError("groth16: a proof element is the point at infinity (degenerate key or witness)")
+            # Krs = sum_priv w_i K_i + sum_j h_j Z_j + s Ar + r Bs1 - r s delta1: five points, through the same kernels
+            h = lambda t: t.cpu().numpy().view(np.uint64)
+            part = lambda k: np.zeros(8, np.uint64) if int(infs[k][0]) else h(outs[k])
+            pts5 = np.stack([part("K"), part("Z"), h(outs["A"]), h(outs["B1"]), self.delta1_words])
+            k_w, k_inf = self.ctx.bn254_g1_msm(pts5, tail(1, 1, s, r, (R - r * s % R) % R))
+            self.ctx2.synchronize()
+            t3 = time.perf_counter()
+            if k_inf or int(infs["B2"][0]):
+                raise ValueError("groth16: a proof element is the point at infinity (degenerate key or witness)")
+            a_w, b_w = h(outs["A"]), h(outs["B2"])
+            f = fp_from_mont_words
+            proof = [f(a_w[0:4]), f(a_w[4:8]), f(b_w[4:8]), f(b_w[0:4]), f(b_w[12:16]), f(b_w[8:12]), f(k_w[0:4]), f(k_w[4:8])]
+            self.last_ms = {"witness_upload_and_scalars": (t1 - t0) * 1e3, "operands_of_compute_h_cross_pcie_beside_A_B1_K_B2": (t2 - t1) * 1e3,
+                            "compute_h_z_and_tails": (t3 - t2) * 1e3, "total": (t3 - t0) * 1e3, "fixed_base": self.fixed}
+            if ev is not None:
+                self.last_ms["r1cs_eval_device"] = ev[0].elapsed_time(ev[1])
+                self.last_ms["r1cs_check"] = bool(check)
+        finally:
+            self._sync_all()
         return proof
 
 
