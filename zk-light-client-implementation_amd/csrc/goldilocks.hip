@@ -245,12 +245,16 @@ gl_ntt_pass_r8_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
 // 15 general multiplications + 17 shifts per 32 butterflies instead of 32 multiplications, and ceil(k / 4) LDS round trips per
 // pass.  LDS tile padded by one element per 16 (unit-stride and stride-16 / stride-8 groups all spread over the banks).
 #define NTT_TJ(e) ((e) + ((e) >> 4))
-template <int G, bool DIT, bool INV, int ZP = 0>
+// UNIT (lean form only): the group with nj == 1 -- no index bits below it, its table block is all ones -- loads no table entries and
+// multiplies by none (goldilocks_ntt_group.cuh); LEAN also takes the shifts by 0 of the canonical in-group values as they are
+template <int G, bool DIT, bool INV, int ZP = 0, bool UNIT = false, bool LEAN = false>
 ZKLC_D void gl_ntt_group_lds(u64 *tile, const u64 *__restrict__ tabJ, u64 nj, u32 base, int pb_low) {
     constexpr int M = 1 << G;
     u64 x[M], t[M - 1 > 0 ? M - 1 : 1];
+    if constexpr (!UNIT) {
 #pragma unroll
-    for (int m = 1; m < M; m++) t[m - 1] = tabJ[(u64)(m - 1) * nj];
+        for (int m = 1; m < M; m++) t[m - 1] = tabJ[(u64)(m - 1) * nj];
+    }
     // NTT_TJ is additive over disjoint bit fields: the lane's part once, the group-index part is wave-uniform (scalar)
     const u32 tjb = NTT_TJ(base);
     // ZP: only the first 2^(G - ZP) elements of the group exist (zero padding of an LDE): the others are neither read nor were
@@ -259,12 +263,13 @@ ZKLC_D void gl_ntt_group_lds(u64 *tile, const u64 *__restrict__ tabJ, u64 nj, u3
     for (int m = 0; m < (M >> ZP); m++) x[m] = tile[tjb + NTT_TJ((u32)m << pb_low)];
 #pragma unroll
     for (int m = (M >> ZP); m < M; m++) x[m] = 0;
-    gl_ntt_group_regs<G, DIT, INV, ZP>(x, t);
+    gl_ntt_group_regs<G, DIT, INV, ZP, UNIT, LEAN>(x, t);
 #pragma unroll
     for (int m = 0; m < M; m++) tile[tjb + NTT_TJ((u32)m << pb_low)] = x[m];
 }
 
-template <bool DIT, bool INV>
+// LEAN = false: the forms of rounds 4-6 throughout (ZKLC_LEAN_ARITH=0)
+template <bool DIT, bool INV, bool LEAN>
 __global__ void __launch_bounds__(NTT_THREADS_MAX)
 gl_ntt_pass_g4_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t in_stride, size_t out_stride, ntt_pass p,
                       const u64 *__restrict__ tab, const u64 *__restrict__ scale_hi, const u64 *__restrict__ scale_lo) {
@@ -350,6 +355,28 @@ gl_ntt_pass_g4_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
         const u64 nj = 1ULL << (mg + lowbits);
         const u64 *gtab = tab + p.goff[gi_];
         const u32 n_groups = (u32)tile_n >> g;
+        if constexpr (LEAN) {
+            if (nj == 1) {       // the unit-twiddle group (J = 0 only): no table loads, no multiplications; a loop of its own
+                for (u32 gi = tid; gi < n_groups; gi += n_threads) {
+                    const u32 base = ((gi >> pb_low) << (pb_low + g)) | (gi & ((1u << pb_low) - 1));
+                    if (!DIT && zskip && gi_ == 0) {   // a one-group LDE (2^0..2^1 -> 2^3..2^4): zero-aware and unit at once
+                        if (g == 4)
+                            gl_ntt_group_lds<4, DIT, INV, DIT ? 0 : 3, true, true>(tile, gtab, nj, base, pb_low);
+                        else
+                            gl_ntt_group_lds<3, DIT, INV, DIT ? 0 : 3, true, true>(tile, gtab, nj, base, pb_low);
+                    } else if (g == 4)
+                        gl_ntt_group_lds<4, DIT, INV, 0, true, true>(tile, gtab, nj, base, pb_low);
+                    else if (g == 3)
+                        gl_ntt_group_lds<3, DIT, INV, 0, true, true>(tile, gtab, nj, base, pb_low);
+                    else if (g == 2)
+                        gl_ntt_group_lds<2, DIT, INV, 0, true, true>(tile, gtab, nj, base, pb_low);
+                    else
+                        gl_ntt_group_lds<1, DIT, INV, 0, true, true>(tile, gtab, nj, base, pb_low);
+                }
+                __syncthreads();
+                continue;
+            }
+        }
         for (u32 gi = tid; gi < n_groups; gi += n_threads) {
             u32 base = ((gi >> pb_low) << (pb_low + g)) | (gi & ((1u << pb_low) - 1));
             u64 lowc = base & ((1u << p.c) - 1);
@@ -358,20 +385,22 @@ gl_ntt_pass_g4_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
             if constexpr (!DIT) {
                 if (zskip && gi_ == 0) {               // wave-uniform
                     if (g == 4)
-                        gl_ntt_group_lds<4, DIT, INV, 3>(tile, gtab + J, nj, base, pb_low);
+                        gl_ntt_group_lds<4, DIT, INV, 3, false, LEAN>(tile, gtab + J, nj, base, pb_low);
                     else
-                        gl_ntt_group_lds<3, DIT, INV, 3>(tile, gtab + J, nj, base, pb_low);
+                        gl_ntt_group_lds<3, DIT, INV, 3, false, LEAN>(tile, gtab + J, nj, base, pb_low);
                     continue;
                 }
             }
+            // the plain four-stage group of a forward-order (DIF) pass keeps gl_mul_2exp at its shifts by 0: without those four
+            // instructions per butterfly the kernel allocates 129 VGPRs instead of 128 -- three waves per SIMD instead of four
             if (g == 4)
-                gl_ntt_group_lds<4, DIT, INV>(tile, gtab + J, nj, base, pb_low);
+                gl_ntt_group_lds<4, DIT, INV, 0, false, LEAN && DIT>(tile, gtab + J, nj, base, pb_low);
             else if (g == 3)
-                gl_ntt_group_lds<3, DIT, INV>(tile, gtab + J, nj, base, pb_low);
+                gl_ntt_group_lds<3, DIT, INV, 0, false, LEAN>(tile, gtab + J, nj, base, pb_low);
             else if (g == 2)
-                gl_ntt_group_lds<2, DIT, INV>(tile, gtab + J, nj, base, pb_low);
+                gl_ntt_group_lds<2, DIT, INV, 0, false, LEAN>(tile, gtab + J, nj, base, pb_low);
             else
-                gl_ntt_group_lds<1, DIT, INV>(tile, gtab + J, nj, base, pb_low);
+                gl_ntt_group_lds<1, DIT, INV, 0, false, LEAN>(tile, gtab + J, nj, base, pb_low);
         }
         __syncthreads();
     }
@@ -679,9 +708,11 @@ static int32_t gl_ntt_run(zklc_ctx *ctx, hipStream_t st, const u64 *in, size_t i
     static const bool r8 = getenv("ZKLC_NTT_R8") != nullptr;           // A/B switch: radix-8 groups with a table twiddle per butterfly
     const bool lds_ok = zklc_once_per_device([] {     // 72 KB of dynamic LDS is above the default 64 KB cap
         const int bytes = ((1 << NTT_TILE_LOG_BIG) + (1 << NTT_TILE_LOG_BIG) / 8) * (int)sizeof(u64);
-        const void *fns[6] = {(const void *)gl_ntt_pass_r8_kernel<true>,        (const void *)gl_ntt_pass_r8_kernel<false>,
-                              (const void *)gl_ntt_pass_g4_kernel<true, true>,  (const void *)gl_ntt_pass_g4_kernel<true, false>,
-                              (const void *)gl_ntt_pass_g4_kernel<false, true>, (const void *)gl_ntt_pass_g4_kernel<false, false>};
+        const void *fns[10] = {(const void *)gl_ntt_pass_r8_kernel<true>,               (const void *)gl_ntt_pass_r8_kernel<false>,
+                               (const void *)gl_ntt_pass_g4_kernel<true, true, true>,   (const void *)gl_ntt_pass_g4_kernel<true, false, true>,
+                               (const void *)gl_ntt_pass_g4_kernel<false, true, true>,  (const void *)gl_ntt_pass_g4_kernel<false, false, true>,
+                               (const void *)gl_ntt_pass_g4_kernel<true, true, false>,  (const void *)gl_ntt_pass_g4_kernel<true, false, false>,
+                               (const void *)gl_ntt_pass_g4_kernel<false, true, false>, (const void *)gl_ntt_pass_g4_kernel<false, false, false>};
         for (const void *f : fns) {
             hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
             if (e != hipSuccess) return e;
@@ -792,14 +823,14 @@ static int32_t gl_ntt_run(zklc_ctx *ctx, hipStream_t st, const u64 *in, size_t i
             const unsigned threads = tile_log > NTT_TILE_LOG_MAX ? NTT_THREADS_MAX : NTT_THREADS;
             const size_t lds = ((size_t(1) << tile_log) + (size_t(1) << tile_log) / 16) * sizeof(u64);
             const u64 *sh = (const u64 *)ctx->gl_scale_hi, *sl = (const u64 *)ctx->gl_scale_lo;
-            if (dit && inverse)
-                hipLaunchKernelGGL((gl_ntt_pass_g4_kernel<true, true>), grid, dim3(threads), lds, st, src, out, sstride, out_stride, p, tw, sh, sl);
-            else if (dit)
-                hipLaunchKernelGGL((gl_ntt_pass_g4_kernel<true, false>), grid, dim3(threads), lds, st, src, out, sstride, out_stride, p, tw, sh, sl);
-            else if (inverse)
-                hipLaunchKernelGGL((gl_ntt_pass_g4_kernel<false, true>), grid, dim3(threads), lds, st, src, out, sstride, out_stride, p, tw, sh, sl);
+            void (*fn)(const u64 *, u64 *, size_t, size_t, ntt_pass, const u64 *, const u64 *, const u64 *);
+            if (zklc_lean_arith())
+                fn = dit ? (inverse ? gl_ntt_pass_g4_kernel<true, true, true> : gl_ntt_pass_g4_kernel<true, false, true>)
+                         : (inverse ? gl_ntt_pass_g4_kernel<false, true, true> : gl_ntt_pass_g4_kernel<false, false, true>);
             else
-                hipLaunchKernelGGL((gl_ntt_pass_g4_kernel<false, false>), grid, dim3(threads), lds, st, src, out, sstride, out_stride, p, tw, sh, sl);
+                fn = dit ? (inverse ? gl_ntt_pass_g4_kernel<true, true, false> : gl_ntt_pass_g4_kernel<true, false, false>)
+                         : (inverse ? gl_ntt_pass_g4_kernel<false, true, false> : gl_ntt_pass_g4_kernel<false, false, false>);
+            hipLaunchKernelGGL(fn, grid, dim3(threads), lds, st, src, out, sstride, out_stride, p, tw, sh, sl);
         } else if (radix2) {
             if (dit)
                 hipLaunchKernelGGL(gl_ntt_pass_kernel<true>, grid, dim3(NTT_THREADS), 0, st, src, out, sstride, out_stride, p, tw,

@@ -33,6 +33,11 @@ ZKLC_HD u64 gl_mul_2exp(u64 x, u32 e) {
     return gl_sub((a0 << 32) - a0, a1 + (th << 32));  // both operands canonical: (2^32-1)^2 < p, a1 + th 2^32 < 2^63 + 2^32
 }
 
+// the same for an x that is known to be canonical (every operand inside a group is: gl_add, gl_sub, gl_reduce128 and the
+// multiplications return canonical values and the transforms take canonical input): a shift by 0 is the value itself, where
+// gl_mul_2exp still has to compare with p (15 of the 32 butterflies of a 4-stage group, 7 of the 12 of a 3-stage group)
+ZKLC_HD u64 gl_mul_2exp_canonical(u64 x, u32 e) { return e == 0 ? x : gl_mul_2exp(x, e); }
+
 // x[i] = x[i] * t[i] (canonical results), i < N.  On the device in batches of four / three / two independent multiplications per
 // asm statement (tools/gen_gl_asm.py -> goldilocks_mul_asm.inc: 19 instructions per multiplication, carries in SGPR pairs, the
 // batch interleaved so that no flag is read within two slots of its write); the compiler's gl_mul is 28.
@@ -100,11 +105,17 @@ ZKLC_HD constexpr u32 gl_bitrev_small(u32 m, int g) {
 // A butterfly of stage u < ZP then has b = 0: x[m] stays, x[m | bit] = +-a * 2^e -- one shift instead of add + sub + shift -- and
 // the butterflies whose two inputs are both zero are not evaluated at all (G = 4, ZP = 3: 2 + 4 + 8 shifts and the 8 butterflies
 // of the last stage instead of 32 butterflies).  x[m] for m >= 2^(G - ZP) need not be initialised.
-template <int G, bool DIT, bool INV, int ZP = 0>
+//
+// UNIT: the group has no index bits below it (J = 0 only: the lowest stages of the pass that holds stage logn - 1 -- the last
+// group of a DIF transform, the first a DIT transform executes).  Its table block is all ones, w^((bitrev_g(m) * 0) << s'), so the
+// M - 1 multiplications are left out and t is not read (the caller loads nothing).
+// CANON: x is canonical on entry (the contract of the transforms), so the shifts by 0 are gl_mul_2exp_canonical.  UNIT = CANON =
+// false is the form of rounds 4-6 (ZKLC_LEAN_ARITH=0).
+template <int G, bool DIT, bool INV, int ZP = 0, bool UNIT = false, bool CANON = false>
 ZKLC_HD void gl_ntt_group_regs(u64 *x, const u64 *t) {
     constexpr int M = 1 << G;
     static_assert(ZP >= 0 && ZP <= G && (ZP == 0 || !DIT), "zero-padded form: DIF groups only");
-    if (DIT) gl_mul_batch<M - 1>(x + 1, t);
+    if (DIT && !UNIT) gl_mul_batch<M - 1>(x + 1, t);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
@@ -125,21 +136,23 @@ ZKLC_HD void gl_ntt_group_regs(u64 *x, const u64 *t) {
                 const int zmask = ((1 << (bit + 1)) - 1) & ~((1 << (G - ZP)) - 1);
                 if (m & zmask) continue;
                 const u64 a0 = x[m];
-                x[m | (1 << bit)] = gl_mul_2exp(neg ? gl_sub(0, a0) : a0, sh);
+                const u64 a1 = neg ? gl_sub(0, a0) : a0;
+                x[m | (1 << bit)] = CANON ? gl_mul_2exp_canonical(a1, sh) : gl_mul_2exp(a1, sh);
                 continue;
             }
             u64 a = x[m], b = x[m | (1 << bit)];
             if (DIT) {
-                b = gl_mul_2exp(b, sh);
+                b = CANON ? gl_mul_2exp_canonical(b, sh) : gl_mul_2exp(b, sh);
                 x[m] = neg ? gl_sub(a, b) : gl_add(a, b);
                 x[m | (1 << bit)] = neg ? gl_add(a, b) : gl_sub(a, b);
             } else {
                 x[m] = gl_add(a, b);
-                x[m | (1 << bit)] = gl_mul_2exp(neg ? gl_sub(b, a) : gl_sub(a, b), sh);
+                const u64 d = neg ? gl_sub(b, a) : gl_sub(a, b);
+                x[m | (1 << bit)] = CANON ? gl_mul_2exp_canonical(d, sh) : gl_mul_2exp(d, sh);
             }
         }
     }
-    if (!DIT) gl_mul_batch<M - 1>(x + 1, t);
+    if (!DIT && !UNIT) gl_mul_batch<M - 1>(x + 1, t);
 }
 
 // the same group written the plain way: every butterfly with its full twiddle w^(...) (the definition above); the check of

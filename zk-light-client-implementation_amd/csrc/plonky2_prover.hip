@@ -21,6 +21,7 @@
 #include <string.h>
 #include "plonky2_gates.cuh"
 #include "plonky2_host.h"
+#include "plonky2_perm_terms.cuh"
 #include "zklc_internal.h"
 
 #define P2_THREADS 256
@@ -43,6 +44,24 @@ __global__ void p2_scale_by_powers_kernel(u64 *data, u64 base, u64 n) {
     *p = gl_mul(*p, gl_pow(base, j));
 }
 
+// the same with one exponentiation per eight elements (the lean form): a lane takes j, j + 256, ..., j + 7 * 256 -- a wave still reads
+// and writes whole 512-byte runs -- and steps its power by step = base^256 (from the host)
+#define P2_SCALE_PER_LANE 8
+__global__ void __launch_bounds__(256) p2_scale_by_powers_strided_kernel(u64 *data, u64 base, u64 step, u64 n) {
+    const u64 j0 = (u64)blockIdx.x * (256 * P2_SCALE_PER_LANE) + threadIdx.x;
+    if (j0 >= n) return;
+    u64 *p = data + (size_t)blockIdx.y * n;
+    u64 v[P2_SCALE_PER_LANE];
+#pragma unroll
+    for (int q = 0; q < P2_SCALE_PER_LANE; q++) v[q] = j0 + 256 * q < n ? p[j0 + 256 * q] : 0;
+    u64 pw = gl_pow(base, j0);
+#pragma unroll
+    for (int q = 0; q < P2_SCALE_PER_LANE; q++) {
+        if (j0 + 256 * q < n) p[j0 + 256 * q] = gl_mul(v[q], pw);
+        if (q + 1 < P2_SCALE_PER_LANE) pw = gl_mul(pw, step);
+    }
+}
+
 // out[j] = z^j (extension)
 __global__ void p2_ext_powers_kernel(gl2 *out, gl2 z, u64 n) {
     u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -61,6 +80,8 @@ __global__ void p2_ext_pow_limbs_kernel(u32 *out, gl2 z, u32 n) {
 // ---------------------------------------------------------------------------------------- Z and partial products
 // prover.rs `wires_permutation_partial_products_and_zs`: per row the running products of the chunk quotients
 //   rp[k][i] = prod_{k' <= k} prod_{j in chunk k'} (w_j + beta k_j x_i + gamma) / (w_j + beta sigma_j(x_i) + gamma)
+// LEAN: the chunk through p2_perm_chunk_terms (plonky2_perm_terms.cuh); false = the chain as it was (ZKLC_LEAN_ARITH=0)
+template <bool LEAN>
 __global__ void __launch_bounds__(P2_THREADS)
 p2_chunk_products_kernel(const u64 *__restrict__ wires, const u64 *__restrict__ sigmas, const u64 *__restrict__ subgroup,
                          const u64 *__restrict__ k_is, u32 n, u32 routed, u32 qdf, u32 nchunks, u64 beta, u64 gamma,
@@ -72,10 +93,33 @@ p2_chunk_products_kernel(const u64 *__restrict__ wires, const u64 *__restrict__ 
     for (u32 k = 0; k < nchunks; k++) {
         u64 np = 1, dp = 1;
         u32 end = (k + 1) * qdf < routed ? (k + 1) * qdf : routed;
-        for (u32 j = k * qdf; j < end; j++) {
-            u64 w = gl_add(wires[(size_t)j * n + i], gamma);
-            np = gl_mul(np, gl_add(w, gl_mul(beta, gl_mul(k_is[j], x))));
-            dp = gl_mul(dp, gl_add(w, gl_mul(beta, sigmas[(size_t)j * n + i])));
+        if constexpr (LEAN) {
+            const u64 bx = gl_mul(beta, x);
+            for (u32 j = k * qdf; j < end; j += P2_PERM_CHUNK) {
+                const u32 cnt = end - j < P2_PERM_CHUNK ? end - j : P2_PERM_CHUNK;
+                u64 wv[P2_PERM_CHUNK], sv[P2_PERM_CHUNK], kv[P2_PERM_CHUNK], n8, d8;
+#pragma unroll
+                for (u32 q = 0; q < P2_PERM_CHUNK; q++) {
+                    const u32 jq = q < cnt ? j + q : j;      // clamped: never past the last routed column
+                    wv[q] = wires[(size_t)jq * n + i];
+                    sv[q] = sigmas[(size_t)jq * n + i];
+                    kv[q] = k_is[jq];
+                }
+                p2_perm_chunk_terms(wv, sv, kv, cnt, beta, bx, gamma, n8, d8);
+                if (j == k * qdf) {                     // wave-uniform; a chunk of more than eight wires multiplies its parts
+                    np = n8;
+                    dp = d8;
+                } else {
+                    np = gl_mul(np, n8);
+                    dp = gl_mul(dp, d8);
+                }
+            }
+        } else {
+            for (u32 j = k * qdf; j < end; j++) {
+                u64 w = gl_add(wires[(size_t)j * n + i], gamma);
+                np = gl_mul(np, gl_add(w, gl_mul(beta, gl_mul(k_is[j], x))));
+                dp = gl_mul(dp, gl_add(w, gl_mul(beta, sigmas[(size_t)j * n + i])));
+            }
         }
         nums[k] = np;
         dens[k] = dp;
@@ -184,7 +228,11 @@ struct p2_quotient_args {
 // The sum over the vanishing terms is split over launches so that each has a small register footprint (the all-in-one
 // kernel needed 221 VGPRs = 2 waves/SIMD): p2_quotient_base_kernel writes the L_0 and partial-product terms,
 // p2_quotient_gate_kernel<TYPE> adds filter_g * sum_i alpha^(k_gates + i) c_{g,i} for one gate of the list.
-__global__ void __launch_bounds__(P2_THREADS) p2_quotient_base_kernel(p2_quotient_args a) {
+// LEAN: the eight-wire chunks of the partial-product terms through p2_perm_chunk_terms (a chunk of another size -- the last one when
+// the routed wires are no multiple of eight -- stays the chain: its padded form cost this kernel registers it does not have);
+// false = the chains as they were (ZKLC_LEAN_ARITH=0)
+template <bool LEAN>
+__global__ void __launch_bounds__(P2_THREADS, LEAN ? 4 : 1) p2_quotient_base_kernel(p2_quotient_args a) {
     const size_t N = (size_t)1 << a.lde_bits;
     size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= N) return;
@@ -206,12 +254,23 @@ __global__ void __launch_bounds__(P2_THREADS) p2_quotient_base_kernel(p2_quotien
     for (u32 c = 0; c < a.nch; c++) {
         u64 beta = a.ch.beta[c], gamma = a.ch.gamma[c];
         u64 prev = a.zs[(size_t)c * N + p];
+        [[maybe_unused]] const u64 bx = LEAN ? gl_mul(beta, x) : 0;
         for (u32 k = 0; k < nchunks; k++) {
             u64 np = 1, dp = 1;
             u32 end = (k + 1) * a.qdf < a.routed ? (k + 1) * a.qdf : a.routed;
             gl_ktab64 *kis = (gl_ktab64 *)a.k_is;
             u32 j = k * a.qdf;
-            if (end - j == 8) {          // the usual chunk (quotient degree factor 8): sixteen loads in flight
+            if (LEAN && end - j == P2_PERM_CHUNK) {      // the usual chunk (quotient degree factor 8): sixteen loads in flight
+                u64 wv[P2_PERM_CHUNK], sv[P2_PERM_CHUNK], kv[P2_PERM_CHUNK];
+#pragma unroll
+                for (int q = 0; q < P2_PERM_CHUNK; q++) {
+                    wv[q] = a.wires[(size_t)(j + q) * N + p];
+                    sv[q] = a.cs[(size_t)(a.num_constants + j + q) * N + p];
+                    kv[q] = kis[j + q];
+                }
+                p2_perm_chunk_terms(wv, sv, kv, P2_PERM_CHUNK, beta, bx, gamma, np, dp);
+                j = end;
+            } else if (end - j == 8) {          // the usual chunk (quotient degree factor 8): sixteen loads in flight
                 u64 wv[8], sv[8];
 #pragma unroll
                 for (int q = 0; q < 8; q++) {
@@ -833,19 +892,48 @@ struct p2_fri_combine_args {
     gl2 alpha, zeta, g_zeta, y0, y1, alpha_pow_nch;
     gl2 *out;             // [N] extension elements
     const u32 *apow;      // alpha^i, i < sum(widths), as limbs (p2_ext_pow_limbs_kernel)
+    const u64 *xs;        // the circuit's table of LDE points, x = g w^bitrev(p) (the lean form reads x instead of raising w to i)
 };
+// The lean form's denominators: out[p] = (1 / norm(x_p - zeta), 1 / norm(x_p - g zeta)) for the combine kernel to read -- it finds
+// them in the element of `out` it is about to write, so they need no buffer of their own and add 32 bytes per point to the ~3 KB
+// the combination streams.  A lane inverts the sixteen norms of eight consecutive points with one gl_inv (plonky2_perm_terms.cuh).
+__global__ void __launch_bounds__(P2_THREADS) p2_fri_denominators_kernel(const u64 *__restrict__ xs, u32 lde_bits, gl2 zeta, gl2 g_zeta,
+                                                                           gl2 *__restrict__ out) {
+    const size_t N = (size_t)1 << lde_bits;
+    const size_t p0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * P2_FRI_DEN_POINTS;
+    if (p0 >= N) return;
+    u64 x[P2_FRI_DEN_POINTS];
+    gl2 r[P2_FRI_DEN_POINTS];
+#pragma unroll
+    for (int q = 0; q < P2_FRI_DEN_POINTS; q++) x[q] = p0 + q < N ? xs[p0 + q] : 0;      // N < 8: the padding is inverted and dropped
+    p2_fri_den_inverse_norms(x, zeta, g_zeta, r);
+#pragma unroll
+    for (int q = 0; q < P2_FRI_DEN_POINTS; q++)
+        if (p0 + q < N) out[p0 + q] = r[q];
+}
 // fri/oracle.rs `prove_openings` in evaluation form (= fri.go:208-251 on the verifier side):
 //   out(x) = alpha^nch * (sum_i alpha^i p_i(x) - y0) / (x - zeta) + (sum_{i<nch} alpha^i z_i(x) - y1) / (x - g zeta)
 // The sums are NOT evaluated by Horner's rule (one extension multiplication per polynomial and a dependency chain as long as
 // the list): alpha^i comes from a table of 22-bit limbs (p2_ext_pow_limbs_kernel) and every p_i(x) alpha^i is twelve carry-free
 // v_mad_u64_u32 into two column accumulators (gl_acc3_mul) -- ~4 k instructions per point for the 357 polynomials of the
 // Ed25519 circuit instead of ~30 k, which leaves the kernel to the 8 bytes per polynomial and point it has to read.
+//
+// LEAN: x from the circuit's table and the two inverse norms from p2_fri_denominators_kernel (in out[p]) instead of a gl_pow and two
+// base-field inversions -- ~300 multiply-reduces per point beside the combination itself; false = as it was (ZKLC_LEAN_ARITH=0).
+template <bool LEAN>
 __global__ void __launch_bounds__(P2_THREADS) p2_fri_combine_kernel(p2_fri_combine_args a) {
     const size_t N = (size_t)1 << a.lde_bits;
     size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= N) return;
-    u64 i = __brevll((u64)p) >> (64 - a.lde_bits);
-    u64 x = gl_mul(GL_GENERATOR, gl_pow(a.w_lde, i));
+    u64 x;
+    [[maybe_unused]] gl2 ninv = gl2_make(0, 0);
+    if constexpr (LEAN) {
+        x = a.xs[p];
+        ninv = a.out[p];
+    } else {
+        u64 i = __brevll((u64)p) >> (64 - a.lde_bits);
+        x = gl_mul(GL_GENERATOR, gl_pow(a.w_lde, i));
+    }
     gl_acc3 sa = {0, 0, 0}, sb = {0, 0, 0};
     gl_ktab *k6 = (gl_ktab *)a.apow;
     u32 terms = 0;
@@ -883,8 +971,16 @@ __global__ void __launch_bounds__(P2_THREADS) p2_fri_combine_kernel(p2_fri_combi
         gl_acc3_mul(tb, v, (gl_ktab *)a.apow + 12 * (size_t)j + 6);
     }
     gl2 acc1 = gl2_make(gl_acc3_reduce(ta), gl_acc3_reduce(tb));
-    gl2 q0 = gl2_mul(gl2_sub(acc, a.y0), gl2_inv(gl2_sub(gl2_make(x, 0), a.zeta)));
-    gl2 q1 = gl2_mul(gl2_sub(acc1, a.y1), gl2_inv(gl2_sub(gl2_make(x, 0), a.g_zeta)));
+    gl2 i0, i1;
+    if constexpr (LEAN) {
+        i0 = p2_fri_den_inverse(x, a.zeta, ninv.a);
+        i1 = p2_fri_den_inverse(x, a.g_zeta, ninv.b);
+    } else {
+        i0 = gl2_inv(gl2_sub(gl2_make(x, 0), a.zeta));
+        i1 = gl2_inv(gl2_sub(gl2_make(x, 0), a.g_zeta));
+    }
+    gl2 q0 = gl2_mul(gl2_sub(acc, a.y0), i0);
+    gl2 q1 = gl2_mul(gl2_sub(acc1, a.y1), i1);
     a.out[p] = gl2_add(gl2_mul(q0, a.alpha_pow_nch), q1);
 }
 
@@ -1246,7 +1342,8 @@ static int32_t p2_plan_quotient(zklc_plonky2_circuit *c, hipStream_t st) {
                 one.idx[0] = g;
                 hipLaunchKernelGGL(fn, dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a, one);
             } else
-                hipLaunchKernelGGL(p2_quotient_base_kernel, dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
+                hipLaunchKernelGGL(zklc_lean_arith() ? p2_quotient_base_kernel<true> : p2_quotient_base_kernel<false>,
+                               dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
             ZKLC_HIP(ctx, hipEventRecord(e1, st));
             ZKLC_HIP(ctx, hipEventSynchronize(e1));
             float ms = 0;
@@ -1556,7 +1653,8 @@ extern "C" int32_t zklc_plonky2_prove_dev(zklc_ctx *ctx, void *stream, zklc_plon
     P2_PIN(c, grand, u64, P2_MAX_CH);
     for (u32 k = 0; k < P2_MAX_CH; k++) grand[k] = 1;
     for (u32 k = 0; k < nch; k++) {
-        hipLaunchKernelGGL(p2_chunk_products_kernel, dim3((n + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, d_wires,
+        hipLaunchKernelGGL(zklc_lean_arith() ? p2_chunk_products_kernel<true> : p2_chunk_products_kernel<false>,
+                           dim3((n + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, d_wires,
                            (const u64 *)c->d_sigma_vals, (const u64 *)c->d_subgroup, (const u64 *)c->d_kis, n, P.num_routed_wires,
                            P.quotient_degree_factor, c->nchunks, chal.beta[k], chal.gamma[k], c->d_rp);
         hipLaunchKernelGGL(p2_scan_local_kernel, dim3(nblocks), dim3(P2_THREADS), 0, st, (const u64 *)(c->d_rp + (size_t)npp * n),
@@ -1604,7 +1702,8 @@ extern "C" int32_t zklc_plonky2_prove_dev(zklc_ctx *ctx, void *stream, zklc_plon
         if (c->plan.nwaves) {
             hipLaunchKernelGGL(p2_quotient_fused_kernel, dim3(N / 64), dim3(64 * c->plan.nwaves), c->fused_lds, st, a, c->plan);
         } else {
-            hipLaunchKernelGGL(p2_quotient_base_kernel, dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
+            hipLaunchKernelGGL(zklc_lean_arith() ? p2_quotient_base_kernel<true> : p2_quotient_base_kernel<false>,
+                               dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
             static const bool one_per_launch = getenv("ZKLC_P2_GATE_LAUNCH") && !strcmp(getenv("ZKLC_P2_GATE_LAUNCH"), "single");   // A/B
             std::vector<bool> done(P.num_gates, false);
             for (u32 g = 0; g < P.num_gates; g++) {
@@ -1665,7 +1764,13 @@ extern "C" int32_t zklc_plonky2_prove_dev(zklc_ctx *ctx, void *stream, zklc_plon
         ZKLC_HIP(ctx, hipGetLastError());
         // values on g<w_N> (bit-reversed) -> coefficients: inverse DIT, then undo the coset shift
         P2_RC(zklc_gl_ntt_dev(ctx, st, c->d_qv, c->lde_bits, nch, ZKLC_NTT_INVERSE | ZKLC_NTT_IN_BITREV, 0));
-        hipLaunchKernelGGL(p2_scale_by_powers_kernel, dim3((N + 255) / 256, nch), dim3(256), 0, st, c->d_qv, h_inv(GL_GENERATOR), (u64)N);
+        if (zklc_lean_arith()) {
+            const u64 gi = h_inv(GL_GENERATOR);
+            hipLaunchKernelGGL(p2_scale_by_powers_strided_kernel, dim3((N + 256 * P2_SCALE_PER_LANE - 1) / (256 * P2_SCALE_PER_LANE), nch),
+                               dim3(256), 0, st, c->d_qv, gi, h_pow(gi, 256), (u64)N);
+        } else {
+            hipLaunchKernelGGL(p2_scale_by_powers_kernel, dim3((N + 255) / 256, nch), dim3(256), 0, st, c->d_qv, h_inv(GL_GENERATOR), (u64)N);
+        }
         ZKLC_HIP(ctx, hipGetLastError());
         P2_RC(p2_commit_coeffs(c, st, c->quot, quot_cap));
     }
@@ -1737,7 +1842,15 @@ extern "C" int32_t zklc_plonky2_prove_dev(zklc_ctx *ctx, void *stream, zklc_plon
         a.apow = c->d_fri_apow;
         hipLaunchKernelGGL(p2_ext_pow_limbs_kernel, dim3((w0 + w1 + w2 + w3 + 255) / 256), dim3(256), 0, st, c->d_fri_apow, fri_alpha,
                            w0 + w1 + w2 + w3);
-        hipLaunchKernelGGL(p2_fri_combine_kernel, dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
+        a.xs = c->d_xs;
+        if (zklc_lean_arith()) {
+            const u32 lanes = (N + P2_FRI_DEN_POINTS - 1) / P2_FRI_DEN_POINTS;
+            hipLaunchKernelGGL(p2_fri_denominators_kernel, dim3((lanes + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st,
+                               (const u64 *)c->d_xs, c->lde_bits, a.zeta, a.g_zeta, a.out);
+            hipLaunchKernelGGL(p2_fri_combine_kernel<true>, dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
+        } else {
+            hipLaunchKernelGGL(p2_fri_combine_kernel<false>, dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
+        }
         ZKLC_HIP(ctx, hipGetLastError());
         u32 bits = c->lde_bits;
         u64 shift = GL_GENERATOR;

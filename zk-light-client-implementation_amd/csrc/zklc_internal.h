@@ -126,6 +126,14 @@ inline bool zklc_settled_copies() {
     static const bool on = !(getenv("ZKLC_SETTLED_COPIES") && getenv("ZKLC_SETTLED_COPIES")[0] == '0');
     return on;
 }
+// ZKLC_LEAN_ARITH=0 restores, in every kernel at once, the arithmetic forms from before the lean ones (A/B and the parity test):
+// the chained permutation-argument products, the per-point exponentiation and inversions of the FRI combination, the table
+// multiplications of an NTT group whose table block is all ones and its compare-with-p at a shift by 0, one gl_pow per element of
+// the coset unshift.  Field values, and so proof bytes, are the same under both settings.
+inline bool zklc_lean_arith() {
+    static const bool on = !(getenv("ZKLC_LEAN_ARITH") && getenv("ZKLC_LEAN_ARITH")[0] == '0');
+    return on;
+}
 inline hipError_t zklc_readback_async(void *dst, const void *src, size_t bytes, hipStream_t st) {
     if (zklc_settled_copies()) {
         hipError_t e = zklc_stream_wait(st);
