@@ -555,6 +555,46 @@ int32_t zklc_r1cs_abc_dev(zklc_ctx *ctx, void *stream, const zklc_r1cs *s, const
 int32_t zklc_r1cs_abc_host(const zklc_r1cs *s, const uint64_t *witness_regular, uint64_t n, uint64_t *a, uint64_t *b, uint64_t *c,
                            uint32_t flags, uint32_t nthreads, uint64_t *summary);
 
+/* Batched fixed-base scalar multiplication: words[i] = scalars[i] * P for one base P.  Replaces gnark-crypto
+ * `bn254.BatchScalarMultiplicationG1` / `BatchScalarMultiplicationG2` (ecc/bn254/multiexp.go, un-vendored), the calls by which
+ * `groth16.Setup(r1cs)` (gnark-plonky2-verifier/cmd/compile.go:40; gnark backend/groth16/bn254/setup.go) turns the scalars of a
+ * key into its point arrays pk.G1.A / B / K / Z, vk.G1.K and pk.G2.B, and the single multiples alpha, beta, gamma, delta.
+ * The table: ceil(254 / window_bits) rows of 2^window_bits - 1 affine points d 2^(window_bits k) P (64 bytes per G1 point, 128 per
+ * G2 point: zklc_bn254_fixed_base_table_bytes; window_bits 16 = 67 / 134 MB), so that a multiple is at most one mixed addition per
+ * window and no doubling.  group: ZKLC_GROUP_G1 / ZKLC_GROUP_G2.  base_words: the base in gnark-crypto's memory layout (8 / 16 u64,
+ * host pointer), NULL = the generator; it must be a finite point of its curve and of order r -- the decoders above establish that,
+ * it is not tested again; all-zero words (infinity), a group or a window outside 4..16 are ZKLC_ERR_INVALID_ARG.  With a context
+ * the table is built by that context's GPU and stays in its memory (the call returns when it is complete); with ctx = NULL it is
+ * built by host threads for the *_host entries. */
+typedef struct zklc_fixed_base zklc_fixed_base;
+#define ZKLC_GROUP_G1 0u
+#define ZKLC_GROUP_G2 1u
+int32_t zklc_bn254_fixed_base_create(zklc_ctx *ctx, uint32_t group, const uint64_t *base_words, uint32_t window_bits,
+                                     zklc_fixed_base **out);
+void zklc_bn254_fixed_base_destroy(zklc_fixed_base *tbl);
+uint64_t zklc_bn254_fixed_base_table_bytes(uint32_t group, uint32_t window_bits);
+/* bytes of device workspace a multiplication of n scalars needs (X, Y, ZZ, ZZZ and a running product per point: 200 n in G1,
+ * 400 n in G2); 0 for an unknown group or n > 2^30 */
+uint64_t zklc_bn254_fixed_mul_workspace_bytes(uint32_t group, uint64_t n);
+/* d_scalars_regular: n x 4 u64, REGULAR form; a word >= r is reduced, as the multi-exponentiations do.  d_words: n x 8 (G1) / n x 16
+ * (G2) u64, affine points in gnark-crypto's memory layout, canonical; all zero for a scalar = 0 mod r (the point at infinity, as
+ * the multi-exponentiations read it).  d_summary: 2 u64 -- the number of points at infinity and the index of the first one
+ * (all-ones: none).  One inversion is shared by 16 points (the workspace is where they meet).  Enqueue only: nothing is read
+ * back.  ZKLC_ERR_INVALID_ARG for n > 2^30, a missing pointer, a scalar / output / workspace pointer not 16-byte aligned (summary:
+ * 8), workspace_bytes below zklc_bn254_fixed_mul_workspace_bytes, a table of the other group, or one built without a context / on
+ * another GPU.  The workspace holds the multiples of the caller's scalars until it is overwritten. */
+int32_t zklc_bn254_g1_fixed_mul_dev(zklc_ctx *ctx, void *stream, const zklc_fixed_base *tbl, const uint64_t *d_scalars_regular,
+                                    uint64_t n, uint64_t *d_words, uint64_t *d_summary, void *d_workspace, uint64_t workspace_bytes);
+int32_t zklc_bn254_g2_fixed_mul_dev(zklc_ctx *ctx, void *stream, const zklc_fixed_base *tbl, const uint64_t *d_scalars_regular,
+                                    uint64_t n, uint64_t *d_words, uint64_t *d_summary, void *d_workspace, uint64_t workspace_bytes);
+/* the same on the host only (the same lane functions compiled for the host), 256 scalars per task on up to nthreads threads
+ * (0 = 16), over a table created with ctx = NULL: host pointers with the same alignment rule; bit for bit the words and the
+ * summary of the kernels.  Its own workspace is cleared before it is freed. */
+int32_t zklc_bn254_g1_fixed_mul_host(const zklc_fixed_base *tbl, const uint64_t *scalars_regular, uint64_t n, uint32_t nthreads,
+                                     uint64_t *words, uint64_t *summary);
+int32_t zklc_bn254_g2_fixed_mul_host(const zklc_fixed_base *tbl, const uint64_t *scalars_regular, uint64_t n, uint32_t nthreads,
+                                     uint64_t *words, uint64_t *summary);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,17 @@ _SIGS = {
                                            ctypes.c_uint32, _u8p, _u8p, ctypes.c_uint64]),
     "zklc_r1cs_abc_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32,
                                             _u8p]),
+    # batched fixed-base scalar multiplication (the point stage of groth16.Setup)
+    "zklc_bn254_fixed_base_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, _u8p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
+    "zklc_bn254_fixed_base_destroy": (None, [ctypes.c_void_p]),
+    "zklc_bn254_fixed_base_table_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    "zklc_bn254_fixed_mul_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint64]),
+    "zklc_bn254_g1_fixed_mul_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _u8p,
+                                                     _u8p, ctypes.c_uint64]),
+    "zklc_bn254_g2_fixed_mul_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _u8p,
+                                                     _u8p, ctypes.c_uint64]),
+    "zklc_bn254_g1_fixed_mul_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p]),
+    "zklc_bn254_g2_fixed_mul_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p]),
     "zklc_bn254_fr_ntt": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,

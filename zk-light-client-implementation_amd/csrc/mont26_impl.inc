@@ -70,7 +70,7 @@ ZKLC_HD MONT_T MONT_FN(mont_reduce)(i64 *t) {
     for (int j = 0; j < 9; j++) {
         i64 c = (t[10 + j] + ((i64)1 << 25)) >> 26;
         t[11 + j] += c;
-        r.v[j] = (i32)(t[10 + j] - (c << 26));
+        r.v[j] = (i32)(t[10 + j] - (i64)((u64)c << 26));   // (shifted as unsigned: c may be negative)
     }
     r.v[9] = (i32)t[19];
     return r;
