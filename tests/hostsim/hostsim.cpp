@@ -426,6 +426,19 @@ void hostsim_msm_plan(u64 n, u32 *out8) {
     out8[0] = pl.n_pad; out8[1] = pl.c; out8[2] = pl.windows; out8[3] = pl.buckets_per_window; out8[4] = pl.total_buckets;
     out8[5] = pl.chunks; out8[6] = pl.chunk_len; out8[7] = MSM_SEG;
 }
+// the plan of an operand of n points as the library makes it: g1 = 1 for a G1 sum (the endomorphism split is on between
+// MSM_GLV_MIN_POINTS and MSM_GLV_MAX_POINTS), 0 for a G2 or fixed-base sum; out9 = the eight words of hostsim_msm_plan + glv
+void hostsim_msm_plan_group(u64 n, u32 g1, u32 *out9) {
+    msm_plan pl = msm_make_plan(n, g1 != 0);
+    out9[0] = pl.n_pad; out9[1] = pl.c; out9[2] = pl.windows; out9[3] = pl.buckets_per_window; out9[4] = pl.total_buckets;
+    out9[5] = pl.chunks; out9[6] = pl.chunk_len; out9[7] = MSM_SEG; out9[8] = pl.glv;
+}
+// the path zklc_bn254_fr_ntt_dev takes for a natural-order transform of 2^log_n points: out3 = t1, t2 of the two-pass split and
+// whether the size is inside the two-pass window (outside it the one-launch-per-stage path runs)
+void hostsim_fr_ntt_plan(u32 log_n, u32 *out3) {
+    frn_plan p = frn_make_plan(log_n);
+    out3[0] = p.t1; out3[1] = p.t2; out3[2] = (log_n >= FRN_FAST_MIN_LOG && log_n <= FRN_FAST_MAX_LOG) ? 1u : 0u;
+}
 int hostsim_msm_digit_roundtrip(const u64 *scalar4, u32 c, int *digits, u32 *codes) {
     u32 sw[8], carry = 0, windows = 254 / c + 1;
     msm_load_scalar(scalar4, 0, sw);

@@ -299,6 +299,183 @@ def test_fr_ntt_roundtrip_and_coset_property_2p18(zctx):
     assert ev == [(g2n * pow(w, k * n, FR.R) - 1) % FR.R for k in range(8)]
 
 
+# ---- the Fr NTT at every size of the two-pass window (2^12 .. 2^22) and one beyond each end, against the definition
+def _ntt_path(hostsim, log_n):
+    """(t1, t2, two_pass) from the plan function of csrc/bn254_fr_ntt_tile.cuh, asserted against what the sizes are chosen for"""
+    import groth16_size_cases as S
+    t1, t2, two_pass = S.fr_ntt_plan(hostsim, log_n)
+    assert t1 + t2 == log_n and t1 - t2 == log_n % 2 and two_pass == (12 <= log_n <= 22)
+    return t1, t2, two_pass
+
+
+def _mont_rows(vals):
+    import groth16_size_cases as S
+    return S.mont_words_from_ints(vals)
+
+
+MODES = ((0, 0), (0, 1), (1, 0), (1, 1))          # (inverse, coset)
+
+
+@pytest.mark.parametrize("kind", ["random", "all_minus_one", "alternating_0_minus_one"])
+@pytest.mark.parametrize("log_n", [11, 14, 15])
+def test_fr_ntt_matches_the_oracle_transform_2p11_2p14_2p15(zctx, hostsim, log_n, kind):
+    """the whole output against oracle.bn254_fr.ntt in the four (inverse, coset) modes: 2^11 is the last size of the
+    one-launch-per-stage path, 2^14 (7 + 7) and 2^15 (8 + 7, odd split) take the two-pass path"""
+    from oracle import bn254_fr as FR
+    import groth16_size_cases as S
+    import random
+    t1, t2, two_pass = _ntt_path(hostsim, log_n)
+    assert (t1, t2, two_pass) == {11: (6, 5, False), 14: (7, 7, True), 15: (8, 7, True)}[log_n]
+    n = 1 << log_n
+    rng = random.Random(100 + log_n)
+    a = {"random": lambda: [rng.randrange(FR.R) for _ in range(n)], "all_minus_one": lambda: [FR.R - 1] * n,
+         "alternating_0_minus_one": lambda: [0, FR.R - 1] * (n // 2)}[kind]()
+    words = _mont_rows(a)
+    for inverse, coset in MODES:
+        got = S.ints_from_mont_words(zctx.bn254_fr_ntt(words, flags=inverse, coset=coset))
+        assert got == FR.ntt(a, inverse=bool(inverse), coset=bool(coset)), (inverse, coset)
+
+
+@pytest.mark.parametrize("log_n", list(range(11, 24)))
+def test_fr_ntt_structured_inputs_have_their_closed_form_outputs(zctx, hostsim, log_n):
+    """2^11 and 2^23 take the one-launch-per-stage path, 2^12 .. 2^22 the two-pass path with the split (t1, t2) the plan function
+    gives (t1 = t2 + 1 at the odd sizes).  The inputs and their closed-form outputs are tests/fr_ntt_cases.py's: constants (exact
+    zero words in all but one output, checked over the whole array) and eight coefficients at positions that cross the tile
+    decomposition, in the four (inverse, coset) modes; 2^23 (0.8 GB on the device): the two forward modes only."""
+    import fr_ntt_cases as N
+    t1, t2, two_pass = _ntt_path(hostsim, log_n)
+    N.check_structured_inputs(lambda words, inverse, coset: zctx.bn254_fr_ntt(words, flags=inverse, coset=coset), log_n, t1, t2,
+                              N.MODES if log_n < 23 else N.MODES[:2])
+
+
+# ---- computeH and its pointwise kernel on their own
+def _bare_prover(zctx, log_n):
+    """the smallest key the constructor accepts: enough for compute_h (one wire, no private wire, n - 1 points at infinity)"""
+    from zklc_amd.groth16 import Groth16Prover
+    n = 1 << log_n
+    z8, z16 = np.zeros((1, 8), dtype=np.uint64), np.zeros((1, 16), dtype=np.uint64)
+    return Groth16Prover(zctx, {"n": n, "n_public": 0, "A_words": z8, "B1_words": z8, "B2_words": z16, "K_words": np.zeros((0, 8), dtype=np.uint64),
+                                "Z_words": np.zeros((n - 1, 8), dtype=np.uint64), "alpha1_words": z8, "beta1_words": z8, "delta1_words": z8,
+                                "beta2_words": z16, "delta2_words": z16})
+
+
+def _compute_h(prover, abc):
+    import groth16_size_cases as S
+    d_h = prover.compute_h(*[_mont_rows(v) for v in abc])
+    return S.ints_from_words(d_h.cpu().numpy().view(np.uint64))          # compute_h leaves REGULAR form
+
+
+@pytest.mark.parametrize("log_n", [12, 13, 14, 15])
+def test_compute_h_equals_the_oracle_on_the_two_systems(zctx, hostsim, log_n):
+    """Groth16Prover.compute_h (seven transforms on the two-pass path -- splits 6 + 6, 7 + 6, 7 + 7, 8 + 7 -- and the pointwise
+    kernel over n / 256 workgroups) against oracle.groth16.compute_h on A w, B w, C w of the uniform and of the mostly-bits system;
+    a satisfying witness: the top coefficient of h is exact zero"""
+    from oracle import groth16 as G
+    import groth16_size_cases as S
+    t1, t2, two_pass = _ntt_path(hostsim, log_n)
+    assert two_pass and (t1, t2) == {12: (6, 6), 13: (7, 6), 14: (7, 7), 15: (8, 7)}[log_n]
+    prover = _bare_prover(zctx, log_n)
+    try:
+        for kind in ("chain", "bits"):
+            abc = S.system(kind, log_n)["abc"]
+            got = _compute_h(prover, abc)
+            assert got == G.compute_h(*abc), kind
+            assert got[-1] == 0
+    finally:
+        prover.close()
+
+
+@pytest.mark.parametrize("kind", ["all_minus_one", "random"])
+def test_compute_h_on_arbitrary_operands_at_2p13(zctx, hostsim, kind):
+    """operands that do not satisfy a b = c on the domain (the oracle's compute_h is defined anyway: the division by Z on the coset is
+    exact in the field, h just has n coefficients): constant r - 1 in all three, and random; two-pass path, split 7 + 6"""
+    from oracle import groth16 as G
+    import random
+    assert _ntt_path(hostsim, 13) == (7, 6, True)
+    n = 1 << 13
+    rng = random.Random(13)
+    abc = [[G.R - 1] * n] * 3 if kind == "all_minus_one" else [[rng.randrange(G.R) for _ in range(n)] for _ in range(3)]
+    prover = _bare_prover(zctx, 13)
+    try:
+        assert _compute_h(prover, abc) == G.compute_h(*abc)
+    finally:
+        prover.close()
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 1000])
+def test_fr_mul_sub_scale_kernel_against_python_integers(zctx, n):
+    """zklc_bn254_fr_mul_sub_scale_dev, a <- (a b - c) scale, on its own (no transform around it): one element, one short of / exactly
+    / one past a workgroup of 256, several workgroups with a tail; operand triples from {r - 1, 2^255 mod r, random, 0, 1}^3,
+    scale in {1, r - 1, 1 / (5^4096 - 1)}; b aliasing a (a square); the refusals"""
+    import itertools
+    import random
+    import torch
+    import groth16_size_cases as S
+    from oracle import bn254_fr as FR
+    Rr = FR.R
+    rng = random.Random(n)
+    dev = torch.device("cuda", zctx.device_id)
+    pick = lambda v: rng.randrange(Rr) if v is None else v
+    combos = list(itertools.product([Rr - 1, (1 << 255) % Rr, None, 0, 1], repeat=3))
+    assert len(combos) == 125
+    trip = [[pick(v) for v in combos[i % 125]] for i in range(n)]
+    a, b, c = ([t[k] for t in trip] for k in range(3))
+    up = lambda vals: torch.from_numpy(S.mont_words_from_ints(vals).view(np.int64)).to(dev)
+    down = lambda t: S.ints_from_mont_words(t.cpu().numpy().view(np.uint64))
+    lib = zctx._lib
+
+    def run(d_a, d_b, d_c, scale, count):
+        sw = S.mont_words_from_ints([scale]).reshape(4)
+        torch.cuda.current_stream(dev).synchronize()
+        rc = lib.zklc_bn254_fr_mul_sub_scale_dev(zctx._h, zctx.stream_ptr(), d_a, d_b, d_c, sw.ctypes.data, count)
+        zctx.synchronize()
+        return rc
+    scales = [1, Rr - 1, pow((pow(FR.GENERATOR, 1 << 12, Rr) - 1) % Rr, Rr - 2, Rr)]
+    for scale in scales:
+        d_a, d_b, d_c = up(a + [7]), up(b), up(c)                # one element behind a[n - 1]: the tail guard must leave it alone
+        assert run(d_a.data_ptr(), d_b.data_ptr(), d_c.data_ptr(), scale, n) == 0
+        got = down(d_a)
+        assert got[:n] == [(x * y - z) * scale % Rr for x, y, z in zip(a, b, c)], scale
+        assert got[n] == 7 and down(d_b) == b and down(d_c) == c
+        d_a, d_c = up(a), up(c)                                  # b aliases a
+        assert run(d_a.data_ptr(), d_a.data_ptr(), d_c.data_ptr(), scale, n) == 0
+        assert down(d_a) == [(x * x - z) * scale % Rr for x, z in zip(a, c)], scale
+    d_a, d_b, d_c = up(a), up(b), up(c)
+    pa, pb, pc = d_a.data_ptr(), d_b.data_ptr(), d_c.data_ptr()
+    sw = S.mont_words_from_ints([1]).reshape(4)
+    INVALID = -1
+    assert run(None, pb, pc, 1, n) == INVALID and run(pa, None, pc, 1, n) == INVALID and run(pa, pb, None, 1, n) == INVALID
+    assert lib.zklc_bn254_fr_mul_sub_scale_dev(zctx._h, zctx.stream_ptr(), pa, pb, pc, None, n) == INVALID
+    assert lib.zklc_bn254_fr_mul_sub_scale_dev(None, zctx.stream_ptr(), pa, pb, pc, sw.ctypes.data, n) == INVALID
+    assert run(pa, pb, pc, Rr - 1, 0) == 0                       # n = 0: OK, nothing launched
+    assert down(d_a) == a and down(d_b) == b and down(d_c) == c, "a refused or empty call wrote"
+
+
+# ---- the plan of the headline proof's G1 sums: no endomorphism split, c = 16, 16 windows
+def test_g1_msm_at_the_first_size_without_the_split(zctx, hostsim):
+    """2^21 + 1 points: the first size where msm_make_plan stops splitting (glv = 0, c = 16, 16 windows of 2^15 buckets) -- the plan
+    of the 2^22 proof's sums -- against the oracle's C Pippenger: uniform scalars, and the same with the first 2^18 witness-like (one
+    bucket per window with ~2^17 entries: the heavy-combine kernel)"""
+    import time
+    import groth16_size_cases as S
+    n = (1 << 21) + 1
+    assert S.msm_plan(hostsim, n - 1, True)["glv"] == 1
+    plan = S.msm_plan(hostsim, n, True)
+    assert (plan["glv"], plan["c"], plan["windows"], plan["buckets_per_window"]) == (0, 16, 16, 1 << 15)
+    rng = np.random.default_rng(21)
+    pts = cport.bn254_gen_points(n, 13, 5)
+    sc = rand_scalars(rng, n)
+    mixed = sc.copy()
+    mixed[:1 << 18] = witness_like(rng, 1 << 18)
+    for name, s in (("uniform", sc), ("witness-like head", mixed)):
+        s = np.ascontiguousarray(s)
+        got, ginf = zctx.bn254_g1_msm(pts, s)
+        t = time.perf_counter()
+        want, winf, _ = cport.bn254_msm(pts, s, nthreads=16)
+        print("oracle msm, 2^21 + 1 points, %s: %.1f s" % (name, time.perf_counter() - t))
+        assert ginf == winf and np.array_equal(got, want), name
+
+
 # ---------------------------------------------------------------- G2 MSM (zklc_bn254_g2_msm)
 def _g2_points(n, seed):
     import random

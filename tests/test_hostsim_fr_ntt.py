@@ -30,3 +30,27 @@ def test_two_pass_walk_matches_definition(hostsim, log_n, inverse, coset):
     a = _to_words(vals)
     hostsim.hostsim_fr_ntt_two_pass(a.ctypes.data_as(ctypes.c_void_p), log_n, inverse, coset)
     assert _from_words(a) == FR.ntt(vals, inverse=bool(inverse), coset=bool(coset))
+
+
+@pytest.mark.parametrize("log_n", [12, 13, 15])
+def test_two_pass_walk_on_inputs_with_closed_form_outputs(hostsim, log_n):
+    """the inputs tests/test_gpu_bn254.py gives the kernels at 2^11 .. 2^23 (tests/fr_ntt_cases.py), through the same lane
+    functions on the CPU at an even split, an odd split and 8 + 7: a constant goes to EXACT zero words in all outputs but one
+    (zeros accumulated lazily through every stage of both passes, then frozen); eight coefficients on the digit boundaries of
+    j = j1 N2 + j2 are checked at outputs on the boundaries of k = k1 + N1 k2"""
+    import fr_ntt_cases as N
+    import groth16_size_cases as S
+    t1, t2, two_pass = S.fr_ntt_plan(hostsim, log_n)
+    assert two_pass and (t1, t2) == ((log_n + 1) // 2, log_n // 2)
+
+    def ntt(words, inverse, coset):
+        a = np.ascontiguousarray(words, dtype=np.uint64).copy()
+        hostsim.hostsim_fr_ntt_two_pass(a.ctypes.data_as(ctypes.c_void_p), log_n, inverse, coset)
+        return a
+    N.check_structured_inputs(ntt, log_n, t1, t2)
+
+
+def test_the_plan_function_names_the_window_of_the_two_pass_path(hostsim):
+    import groth16_size_cases as S
+    assert [S.fr_ntt_plan(hostsim, l) for l in (11, 12, 13, 22, 23)] == [(6, 5, False), (6, 6, True), (7, 6, True), (11, 11, True),
+                                                                        (12, 11, False)]

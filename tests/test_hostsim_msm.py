@@ -130,6 +130,27 @@ def test_plan_and_digit_codes(hostsim):
                     assert (neg, mag) == (d < 0, abs(d))
 
 
+def test_plan_of_a_g1_sum_carries_the_endomorphism_split(hostsim):
+    """hostsim_msm_plan_group: the plan as the library makes it for a G1 sum (split between 256 and 2^21 points: 2 n half-width
+    scalars, half the windows) and for a G2 / fixed-base sum (never split); the first eight words are hostsim_msm_plan's"""
+    plain, out = (ctypes.c_uint32 * 8)(), (ctypes.c_uint32 * 9)()
+    for n in (1, 255, 256, 2047, 1 << 15, 1 << 21, (1 << 21) + 1, 1 << 22):
+        hostsim.hostsim_msm_plan(ctypes.c_uint64(n), plain)
+        hostsim.hostsim_msm_plan_group(ctypes.c_uint64(n), 0, out)
+        assert list(out) == list(plain) + [0]
+        hostsim.hostsim_msm_plan_group(ctypes.c_uint64(n), 1, out)
+        glv = int(256 <= n <= 1 << 21)
+        assert out[8] == glv
+        if glv:
+            assert n <= out[0] // 2 and out[0] < 2 * n + 8 and out[2] == 127 // out[1] + 1
+        else:
+            assert list(out)[:8] == list(plain)
+    hostsim.hostsim_msm_plan_group(ctypes.c_uint64((1 << 21) + 1), 1, out)
+    assert (out[1], out[2], out[8]) == (16, 16, 0)                    # the plan of the 2^22 proof's sums
+    hostsim.hostsim_msm_plan_group(ctypes.c_uint64(1 << 15), 1, out)
+    assert (out[1], out[2], out[8]) == (14, 10, 1)
+
+
 def test_g2_lane_walk_with_quad_doublings_matches_python(hostsim):
     """G2 (coordinates in Fp2) through the same lane code, the final doublings by a quad of lanes (ecq_stage* over Fp2Field, as
     msm_final_kernel runs them since round 4) -- against the oracle's Python G2 arithmetic; scalars with digits in every window"""
