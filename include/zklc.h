@@ -595,6 +595,49 @@ int32_t zklc_bn254_g1_fixed_mul_host(const zklc_fixed_base *tbl, const uint64_t 
 int32_t zklc_bn254_g2_fixed_mul_host(const zklc_fixed_base *tbl, const uint64_t *scalars_regular, uint64_t n, uint32_t nthreads,
                                      uint64_t *words, uint64_t *summary);
 
+/* The scalar stage of `groth16.Setup(r1cs)` (gnark-plonky2-verifier/cmd/compile.go:40; gnark backend/groth16/bn254/setup.go
+ * `setupABC` and the loops around it, un-vendored): from a constraint system of zklc_r1cs_create and the toxic waste to the discrete
+ * logarithms of the key's points, in the form the batched fixed-base multiplication above reads.  With L_j = L_j(tau) the Lagrange
+ * basis of the subgroup of size n generated by w = 5^((r - 1) / n) (gnark-crypto's fft.Domain generator):
+ *   a_t[i] = sum_j A_ji L_j, b_t[i] and c_t[i] likewise, for every wire i (the columns of the three matrices);
+ *   k[i]   = (beta a_t[i] + alpha b_t[i] + c_t[i]) / gamma for i <= n_public (the constant wire and the public inputs: vk.G1.K),
+ *            / delta for the other wires (pk.G1.K);
+ *   z[i]   = tau^i (tau^n - 1) / delta for i < n - 1 (pk.G1.Z).
+ * toxic: tau, alpha, beta, gamma, delta, 5 x 4 u64, REGULAR form, a HOST pointer in both entries; a value >= r is reduced.
+ * n_public: the public inputs WITHOUT the constant wire.  n: the domain size, a power of two, max(2, n_constraints) <= n <= 2^28.
+ * a_t, b_t, k: n_wires x 4 u64 each; z: (n - 1) x 4 u64; REGULAR form, canonical (< r), written in full.  A wire that occurs in no
+ * A (B) column has a_t (b_t) = 0: its key point is the point at infinity.  Every stored value is exact field arithmetic made
+ * canonical, so device, host threads and plain integers agree bit for bit whatever the order of a column's terms.
+ * ZKLC_ERR_INVALID_ARG for gamma or delta = 0 mod r, n not a power of two or outside its range, n_public + 1 > n_wires, more than
+ * 2^30 wires (what the point stage takes), a missing pointer, an output or workspace pointer not 16-byte aligned (toxic: 8),
+ * workspace_bytes below zklc_groth16_setup_workspace_bytes (0 for sizes it refuses), or a system created without a context / on
+ * another GPU; nothing is launched or written then.
+ * The device entry transposes the system on the GPU into the workspace (a counting sort of the terms by (matrix, wire); nothing is
+ * kept in the handle: a key is set up once), takes the Lagrange values as the inverse transform of (1, tau, .., tau^(n-1)), and
+ * sums columns by 1 / 8 / 64 lanes, longer ones than 2048 terms by a wave per segment.  It waits ONCE on its stream, for the sizes
+ * of the column lists, and returns with the rest enqueued.  The workspace holds functions of the toxic waste (tau's powers, the
+ * Lagrange values, c_t) until the caller clears it; its first five u64 are the plan: columns summed by 1, 8, 64 lanes, columns cut
+ * into segments, segments -- what zklc_groth16_setup_plan computes on the host from the system alone (out5: 5 u64). */
+uint64_t zklc_groth16_setup_workspace_bytes(const zklc_r1cs *s, uint64_t n);
+int32_t zklc_groth16_setup_scalars_dev(zklc_ctx *ctx, void *stream, const zklc_r1cs *s, const uint64_t *toxic, uint32_t n_public,
+                                       uint64_t n, uint64_t *d_a_t, uint64_t *d_b_t, uint64_t *d_k, uint64_t *d_z, void *d_workspace,
+                                       uint64_t workspace_bytes);
+/* the same on the host only (the same lane functions compiled for the host; the Lagrange values by the quotient formula with one
+ * inversion per 256), 256 lanes per task on up to nthreads threads (0 = 16): host pointers with the same alignment rule, no GPU and
+ * no context needed; bit for bit the words of the kernels.  Every buffer and every named temporary that held a function of the toxic
+ * waste is overwritten before the call returns (what the compiler keeps in registers or spills inside one field operation is not
+ * reachable from C++ and is not claimed).  toxic is read word by word in both entries: 8-byte alignment is all it needs. */
+int32_t zklc_groth16_setup_scalars_host(const zklc_r1cs *s, const uint64_t *toxic, uint32_t n_public, uint64_t n, uint32_t nthreads,
+                                        uint64_t *a_t, uint64_t *b_t, uint64_t *k, uint64_t *z);
+int32_t zklc_groth16_setup_plan(const zklc_r1cs *s, uint64_t *out5);
+/* milliseconds between device events around the stages of the calling thread's last zklc_groth16_setup_scalars_dev: transposition
+ * (with the call's one wait), powers and z, Lagrange values, column sums, combination; waits for that call's work; returns the
+ * number of doubles written (0: no call of this thread has completed its launches).  The six events belong to the calling thread:
+ * every zklc_groth16_setup_scalars_dev records them on its stream (a setup runs once per key; six records are nothing beside it),
+ * they are created by a thread's first call, replaced when the thread moves to another GPU, and live as long as the thread's
+ * runtime does -- the library has no per-thread teardown and does not destroy them. */
+uint32_t zklc_groth16_setup_last_timings(double *out_ms, uint32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

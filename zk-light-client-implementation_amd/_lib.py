@@ -101,6 +101,14 @@ _SIGS = {
                                                      _u8p, ctypes.c_uint64]),
     "zklc_bn254_g1_fixed_mul_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p]),
     "zklc_bn254_g2_fixed_mul_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p]),
+    # the scalar stage of groth16.Setup
+    "zklc_groth16_setup_workspace_bytes": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64]),
+    "zklc_groth16_setup_scalars_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint32,
+                                                        ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64]),
+    "zklc_groth16_setup_scalars_host": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, _u8p,
+                                                         _u8p, _u8p, _u8p]),
+    "zklc_groth16_setup_plan": (ctypes.c_int32, [ctypes.c_void_p, _u8p]),
+    "zklc_groth16_setup_last_timings": (ctypes.c_uint32, [_u8p, ctypes.c_uint32]),
     "zklc_bn254_fr_ntt": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_workspace_bytes": (ctypes.c_uint64, [ctypes.c_uint32]),
     "zklc_bn254_fr_ntt_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,

@@ -332,6 +332,24 @@ def points_to_words(pts, g2=False):
     return out
 
 
+_MONT_INV = pow(1 << 256, P - 2, P)
+
+
+def words_to_points(words, g2=False):
+    """the inverse of `points_to_words`: uint64 [n, 8] / [n, 16] in gnark-crypto's memory layout -> affine integer tuples (an
+    all-zero record = None, the point at infinity), what `pk_to_gnark_bytes` / `vk_to_gnark_bytes` and the verifiers take"""
+    w = 16 if g2 else 8
+    raw = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, w).tobytes()
+    out = []
+    for i in range(0, len(raw), 8 * w):
+        c = [int.from_bytes(raw[i + 32 * j:i + 32 * j + 32], "little") * _MONT_INV % P for j in range(w // 4)]
+        if not any(c):
+            out.append(None)
+        else:
+            out.append(((c[0], c[1]), (c[2], c[3])) if g2 else (c[0], c[1]))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- batched decoding (C ABI)
 # include/zklc.h zklc_bn254_g{1,2}_decode_{dev,host}: the point arrays of a key file go through the library -- one lane per point
 # on the GPU, or the same lane functions on host threads -- instead of through read_g1 / read_g2 above, which stay the specification

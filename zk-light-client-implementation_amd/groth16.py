@@ -555,3 +555,7 @@ class NativeGroth16Verifier:
         out = np.zeros(4, dtype=np.float64)
         k = self._lib.zklc_groth16_verifier_last_timings(self._v, out.ctypes.data, 4)
         return dict(zip(("upload", "validate_ksum_kernel", "pairing_kernel", "total")[:k], out[:k].tolist()))
+
+
+# ---------------------------------------------------------------------------------------------- groth16.Setup (zklc_amd/groth16_setup.py)
+from .groth16_setup import KeySetup, Setup, setup_host, setup_scalars_dev, setup_scalars_host  # noqa: E402,F401
