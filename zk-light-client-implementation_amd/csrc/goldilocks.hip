@@ -10,7 +10,9 @@
 // 64 lanes of a wave read 64 consecutive u64 = 512 contiguous bytes), so the
 // "transpose to row-major leaves" pass of the CPU prover disappears.
 #include <stdlib.h>
+#include <string.h>
 #include "poseidon_gl.cuh"
+#include "gl_merkle_plan.h"
 #include "goldilocks_ntt_group.cuh"
 #include <mutex>
 #include "zklc_internal.h"
@@ -488,9 +490,59 @@ __global__ void __launch_bounds__(256) gl_merkle_level_kernel(const u64 *__restr
     o[1] = make_ulonglong2(h[2], h[3]);
 }
 
-// ---- cooperative Poseidon for SMALL trees: one permutation per 16-lane group (lane g < 12 holds state element g).
-// A lane-per-permutation kernel needs ~35 k dependent instructions = ~58 us per Merkle level however few nodes the level has;
-// the top ~13 levels of every tree and the small FRI trees are pure latency.  Here a permutation is ~5 k instructions per
+// ---- the tail of a tree, one lane per permutation: a workgroup of T threads owns 2T consecutive digests of level L and hashes them
+// down level by level -- T parents, T/2, ... -- writing every level where the per-level kernel would (the openings read them).  At
+// level j the first T >> (j - 1) threads are live; a wave without a live lane branches round the permutation and executes the two
+// barriers only, so the idle part of the workgroup issues no VALU work (the cooperative subtree kernel below runs all of its 16
+// groups at every level: 80 group-permutations for 31 results).  The first level reads its children from global memory exactly
+// as gl_merkle_level_kernel does, the later ones from LDS (T digests).  Order between two levels as in the cooperative kernel:
+// both children in registers, permute, barrier, parents to LDS and to the level array, barrier.
+// Host side: gl_merkle_plan.h decides which levels go through here and with how many levels per launch -- by default the three
+// levels of 2^14, 2^13 and 2^12 parents, where the cooperative groups would stand several waves deep on every SIMD; a single wave per
+// SIMD is ~43 us per level here against ~19 us cooperative (measured), so the levels below stay cooperative.
+struct gl_tail_levels {
+    u64 *lvl[GL_MERKLE_TAIL_MAX_LEVELS + 1];   // lvl[0] = the children (read), lvl[1..nlev] = the parents' levels (written)
+};
+template <int T>
+__global__ void __launch_bounds__(T) gl_merkle_tail_kernel(gl_tail_levels L, u32 n_children, u32 nlev) {
+    __shared__ ulonglong2 dig[T][2];
+    const u32 tid = threadIdx.x;
+    const u32 base = blockIdx.x * (2 * T);                  // first child of this workgroup
+    u32 width = T;                                          // parents of this workgroup at the current level
+#pragma unroll 1
+    for (u32 j = 1; j <= nlev; j++, width >>= 1) {
+        const u32 gnode = (base >> j) + tid;
+        const bool live = tid < width && gnode < (n_children >> j);
+        u64 h[4];
+        if (live) {
+            ulonglong2 a, b, cc, dd;
+            if (j == 1) {
+                const ulonglong2 *c = reinterpret_cast<const ulonglong2 *>(L.lvl[0] + (size_t)gnode * 8);
+                a = c[0], b = c[1], cc = c[2], dd = c[3];
+            } else {
+                a = dig[2 * tid][0], b = dig[2 * tid][1], cc = dig[2 * tid + 1][0], dd = dig[2 * tid + 1][1];
+            }
+            u64 l[4] = {a.x, a.y, b.x, b.y}, r[4] = {cc.x, cc.y, dd.x, dd.y};
+            poseidon_gl_two_to_one(l, r, h);
+        }
+        __syncthreads();                                    // every live lane has read its two children
+        if (live) {
+            dig[tid][0] = make_ulonglong2(h[0], h[1]);
+            dig[tid][1] = make_ulonglong2(h[2], h[3]);
+            ulonglong2 *o = reinterpret_cast<ulonglong2 *>(L.lvl[j] + (size_t)gnode * 4);
+            o[0] = make_ulonglong2(h[0], h[1]);
+            o[1] = make_ulonglong2(h[2], h[3]);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- cooperative Poseidon: one permutation per 16-lane group (lane g < 12 holds state element g).  Written when a lane-per-permutation
+// kernel took ~35 k dependent instructions (~58 us) per level.  With the generated permutation (15.1 k instructions) a level is
+// ~43 us for one wave per SIMD, a cooperative one ~19 us (measured; the 27 us once quoted for both held for neither): the
+// cooperative form still halves the latency of every level too small to fill the chip, at about thirteen times the
+// wave-instructions per digest, and loses even on latency where its groups are several waves deep per SIMD (gl_merkle_plan.h).
+// Here a permutation is ~5 k instructions per
 // lane: S-box on the lane's own element, the MDS layer as 12 LDS reads of the group's elements (circulant row of lane g), and
 // the partial rounds in the dense form -- S-box on lane 0 only, the same MDS layer, optimised round constants (first layer 12,
 // then one per round) -- which is the same permutation (oracle/poseidon_gl.py::permute_naive, tests/test_oracle_poseidon.py).
@@ -612,7 +664,10 @@ gl_hash_leaves_coop_kernel(const u64 *__restrict__ mat, size_t stride, size_t le
     }
     if (live && g < 4) digests[(size_t)leaf * 4 + g] = s;
 }
-#define PGL_COOP_MAX_NODES (1u << 14)   // above this the lane-per-permutation kernels fill the chip and are cheaper per permutation
+// Above this many nodes a level fills the chip on its own and goes through the per-level kernel; at or below it the levels are fused
+// (gl_merkle_tail_kernel down to 2^12 parents, the cooperative kernels below).  The lane-per-permutation form is the cheaper one per
+// permutation at every size, not only above this bound; the cooperative one is kept where latency decides (gl_merkle_plan.h).
+#define PGL_COOP_MAX_NODES GL_MERKLE_COOP_MAX_NODES
 
 // ---------------------------------------------------------------- host side
 static u64 host_gl_mul(u64 a, u64 b) {
@@ -928,46 +983,61 @@ int32_t zklc_gl_merkle_commit_strided(zklc_ctx *ctx, hipStream_t st, const uint6
                                       uint32_t log_leaves, uint32_t width, uint32_t cap_height, uint64_t *d_tree) {
     ZKLC_HIP(ctx, hipSetDevice(ctx->device));
     u32 n = 1u << log_leaves;
+    // ZKLC_NO_COOP_POSEIDON: per-level lane kernels only.  ZKLC_MERKLE_TAIL=coop: the cooperative kernels for everything of <= 2^14
+    // nodes, as before the tail kernel; =full: the tail kernel down to 16 parents and lane-per-leaf from 64 leaves (A/B and the
+    // parity tests).  ZKLC_MERKLE_TAIL_T = 256 / 512 / 1024 pins the workgroup, ZKLC_MERKLE_TAIL_MIN the default's last level (log2).
     static const bool coop = !getenv("ZKLC_NO_COOP_POSEIDON");
-    if (coop && n <= PGL_COOP_MAX_NODES)
-        hipLaunchKernelGGL(gl_hash_leaves_coop_kernel, dim3((n + PGL_COOP_GROUPS - 1) / PGL_COOP_GROUPS), dim3(256), 0, st, d_mat,
-                           (size_t)stride, (size_t)leaf_stride, width, n, d_tree);
-    else
-        hipLaunchKernelGGL(gl_hash_leaves_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_mat, (size_t)stride, (size_t)leaf_stride,
-                           width, n, d_tree);
-    ZKLC_HIP(ctx, hipGetLastError());
+    static const char *tail_env = getenv("ZKLC_MERKLE_TAIL");
+    static const u32 mode = !coop                                  ? GL_MERKLE_MODE_LANE
+                            : tail_env && !strcmp(tail_env, "coop") ? GL_MERKLE_MODE_COOP
+                            : tail_env && !strcmp(tail_env, "full") ? GL_MERKLE_MODE_FULL
+                                                                    : GL_MERKLE_MODE_TAIL;
+    static const int tail_pin = getenv("ZKLC_MERKLE_TAIL_T") ? atoi(getenv("ZKLC_MERKLE_TAIL_T")) : 0;
+    static const u32 tail_t = tail_pin == 512 || tail_pin == 1024 ? (u32)tail_pin : 256u;
+    static const int min_pin = getenv("ZKLC_MERKLE_TAIL_MIN") ? atoi(getenv("ZKLC_MERKLE_TAIL_MIN")) : 0;
+    static const u32 tail_min_log = min_pin >= 4 && min_pin <= 14 ? (u32)min_pin : GL_MERKLE_TAIL_MIN_LOG;
     // ZKLC_MERKLE_FUSED=0 keeps one launch per level (A/B and the variant parity test)
     static const bool fused = !(getenv("ZKLC_MERKLE_FUSED") && getenv("ZKLC_MERKLE_FUSED")[0] == '0');
-    u64 *level = d_tree;
-    const u32 total = log_leaves - cap_height;
-    for (u32 l = 0; l < total;) {
-        u32 parents = n >> (l + 1);
-        u64 *next = level + (4ULL << (log_leaves - l));
-        if (coop && fused && parents <= PGL_COOP_MAX_NODES && parents >= 16 && total - l >= 2) {
-            // the cooperative levels in groups of up to five per launch: a workgroup hashes 32 digests down to one
-            u32 nlev = total - l < 5 ? total - l : 5;
-            while (nlev > 1 && ((2 * parents) >> nlev) == 0) nlev--;
-            gl_subtree_levels L;
-            u64 *p = level;
-            for (u32 j = 0; j <= nlev; j++) {
-                L.lvl[j] = p;
-                p += 4ULL << (log_leaves - l - j);
-            }
-            for (u32 j = nlev + 1; j < 6; j++) L.lvl[j] = nullptr;
-            hipLaunchKernelGGL(gl_merkle_subtree_coop_kernel, dim3((2 * parents + 31) / 32), dim3(256), 0, st, L, 2 * parents, nlev);
-            ZKLC_HIP(ctx, hipGetLastError());
-            level = L.lvl[nlev];
-            l += nlev;
-            continue;
+    gl_merkle_plan plan;
+    if (!gl_merkle_make_plan(log_leaves, cap_height, tail_t, mode, fused, tail_min_log, &plan)) return ZKLC_ERR_INVALID_ARG;
+    if (plan.leaf_kind == GL_MERKLE_LEAVES_COOP)
+        hipLaunchKernelGGL(gl_hash_leaves_coop_kernel, dim3(plan.leaf_grid), dim3(256), 0, st, d_mat, (size_t)stride, (size_t)leaf_stride,
+                           width, n, d_tree);
+    else
+        hipLaunchKernelGGL(gl_hash_leaves_kernel, dim3(plan.leaf_grid), dim3(256), 0, st, d_mat, (size_t)stride, (size_t)leaf_stride,
+                           width, n, d_tree);
+    ZKLC_HIP(ctx, hipGetLastError());
+    for (u32 k = 0; k < plan.n; k++) {
+        const gl_merkle_launch &P = plan.launch[k];
+        const u32 parents = P.n_children / 2;
+        switch (P.kind) {
+        case GL_MERKLE_TAIL: {
+            gl_tail_levels L;
+            for (u32 j = 0; j <= GL_MERKLE_TAIL_MAX_LEVELS; j++) L.lvl[j] = j <= P.n_levels ? d_tree + P.off[j] : nullptr;
+            if (P.threads == 1024)
+                hipLaunchKernelGGL(gl_merkle_tail_kernel<1024>, dim3(P.grid), dim3(1024), 0, st, L, P.n_children, P.n_levels);
+            else if (P.threads == 512)
+                hipLaunchKernelGGL(gl_merkle_tail_kernel<512>, dim3(P.grid), dim3(512), 0, st, L, P.n_children, P.n_levels);
+            else
+                hipLaunchKernelGGL(gl_merkle_tail_kernel<256>, dim3(P.grid), dim3(256), 0, st, L, P.n_children, P.n_levels);
+            break;
         }
-        if (coop && parents <= PGL_COOP_MAX_NODES)
-            hipLaunchKernelGGL(gl_merkle_level_coop_kernel, dim3((parents + PGL_COOP_GROUPS - 1) / PGL_COOP_GROUPS), dim3(256), 0, st,
-                               (const u64 *)level, next, parents);
-        else
-            hipLaunchKernelGGL(gl_merkle_level_kernel, dim3((parents + 255) / 256), dim3(256), 0, st, (const u64 *)level, next, parents);
+        case GL_MERKLE_SUBTREE_COOP: {
+            gl_subtree_levels L;
+            for (u32 j = 0; j < 6; j++) L.lvl[j] = j <= P.n_levels ? d_tree + P.off[j] : nullptr;
+            hipLaunchKernelGGL(gl_merkle_subtree_coop_kernel, dim3(P.grid), dim3(256), 0, st, L, P.n_children, P.n_levels);
+            break;
+        }
+        case GL_MERKLE_LEVEL_COOP:
+            hipLaunchKernelGGL(gl_merkle_level_coop_kernel, dim3(P.grid), dim3(256), 0, st, (const u64 *)(d_tree + P.off[0]),
+                               d_tree + P.off[1], parents);
+            break;
+        default:
+            hipLaunchKernelGGL(gl_merkle_level_kernel, dim3(P.grid), dim3(256), 0, st, (const u64 *)(d_tree + P.off[0]), d_tree + P.off[1],
+                               parents);
+            break;
+        }
         ZKLC_HIP(ctx, hipGetLastError());
-        level = next;
-        l++;
     }
     return ZKLC_OK;
 }
