@@ -92,6 +92,29 @@ def build_devsim(verbose=True, force=False):
     return DEVSIM_LIB
 
 
+PGD_DIR = os.path.join(HERE, "..", "tests", "poseidon_gate_dev")
+PGD_SRC = os.path.join(PGD_DIR, "poseidon_gate_dev.hip")
+PGD_LIB = os.path.join(PGD_DIR, "libposeidon_gate_dev.so")
+
+
+def poseidon_gate_dev_is_current():
+    deps = [PGD_SRC, os.path.abspath(__file__)] + [p for ext in ("*.cuh", "*.h", "*.inc") for p in glob.glob(os.path.join(CSRC, ext))]
+    return os.path.exists(PGD_LIB) and os.path.getmtime(PGD_LIB) >= _newest(deps)
+
+
+def build_poseidon_gate_dev(verbose=True, force=False):
+    """tests/poseidon_gate_dev/libposeidon_gate_dev.so: the evaluators of the Poseidon gate behind a one-row-per-lane kernel (test
+    infrastructure for tests/test_gpu_poseidon_gate_stmt.py; the library's compiler and FLAGS; a few seconds)."""
+    if force or not poseidon_gate_dev_is_current():
+        r = subprocess.run([HIPCC] + FLAGS + ["-Wno-inline-asm", "-shared", PGD_SRC, "-o", PGD_LIB], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (PGD_SRC, r.stdout, r.stderr))
+        if verbose:
+            print("[zklc build] built", PGD_LIB, file=sys.stderr)
+    return PGD_LIB
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_devsim(force="--force" in sys.argv)
+    build_poseidon_gate_dev(force="--force" in sys.argv)

@@ -29,7 +29,8 @@ enum p2_gate_type {
     P2_U32_ARITHMETIC, P2_U32_ADD_MANY, P2_U32_SUBTRACTION, P2_U32_RANGE_CHECK, P2_COMPARISON,
     P2_U32_INTERLEAVE, P2_UNINTERLEAVE_TO_U32, P2_UNINTERLEAVE_TO_B32, P2_NUM_GATE_TYPES,
     P2_POSEIDON_LAZY = 100,      // 100 + MODE, not gates of the ABI: the A/B evaluators of P2_POSEIDON (ZKLC_P2_POSEIDON_GATE=lazy | lazy1)
-    P2_POSEIDON_LOOSE = 110      // ZKLC_P2_POSEIDON_GATE=loose
+    P2_POSEIDON_LOOSE = 110,     // ZKLC_P2_POSEIDON_GATE=loose
+    P2_POSEIDON_STMT = 120       // ZKLC_P2_POSEIDON_GATE=stmt
 };
 
 // mirrors zklc_plonky2_gate of include/zklc.h
@@ -436,6 +437,149 @@ ZKLC_D void p2_eval_poseidon_lazy(const V &v, p2_consumer &out) {
     }
 #pragma unroll
     for (int i = 0; i < 12; i++) out.emit(gl_sub(s[i], v.w(12 + i)));
+}
+
+// The state of the Poseidon gate's evaluator between constraints (ZKLC_P2_POSEIDON_GATE=stmt), and its three steps.
+// Device: twelve loose words as 32-bit halves, the form the generated statements take their operands in -- kept in that ONE form
+// from the first round to the last (a state that changes between u64 and halves around every statement is held twice across the
+// statements: 32 VGPRs the kernel does not have); the steps are the hash kernel's full-round statements (poseidon_gl_asm.inc) and
+// the statement of the gate's lazy partial block (poseidon_gate_asm.inc, tools/gen_poseidon_gate_asm.py: the block's eleven wires
+// are operands, two S-box streams, the carry-free multiply-accumulates as filler, one fold per linear form; its table is a block of
+// the hash kernel's PGL_ASM_PBLOCKS).  Host, and a device build without the statements: the same steps in C++.
+//   partial_block(w, b):  w[q] <- (the value computed for S-box input q of block b) - w[q], loose;  state <- the words leaving the block
+#include "poseidon_gate_asm.inc"
+struct p2_pgl_state {
+#if defined(ZKLC_PGL_ASM)
+    u32 lo[12], hi[12];
+    ZKLC_M u64 get(int i) const { return (u64)lo[i] | ((u64)hi[i] << 32); }
+    ZKLC_M void set(int i, u64 x) {
+        lo[i] = (u32)x;
+        hi[i] = (u32)(x >> 32);
+    }
+#define P2_PGL_ST lo[0], hi[0], lo[1], hi[1], lo[2], hi[2], lo[3], hi[3], lo[4], hi[4], lo[5], hi[5], lo[6], hi[6], lo[7], hi[7], lo[8], hi[8], \
+                  lo[9], hi[9], lo[10], hi[10], lo[11], hi[11]
+    ZKLC_M void full_round(int layer) { pgl_asm_full_round(P2_PGL_ST, PGL_ASM_RC + 48 * layer); }
+    ZKLC_M void full_round_init() { pgl_asm_full_round_init(P2_PGL_ST, PGL_ASM_FINIT); }
+    ZKLC_M void partial_block(u64 *w, int b) {
+        u32 wl[11], wh[11];
+#pragma unroll
+        for (int q = 0; q < 11; q++) {
+            wl[q] = (u32)w[q];
+            wh[q] = (u32)(w[q] >> 32);
+        }
+        pgl_gate_asm_partial_block(wl[0], wh[0], wl[1], wh[1], wl[2], wh[2], wl[3], wh[3], wl[4], wh[4], wl[5], wh[5], wl[6], wh[6], wl[7],
+                                   wh[7], wl[8], wh[8], wl[9], wh[9], wl[10], wh[10], P2_PGL_ST, PGL_ASM_PBLOCKS + PGL_GATE_BLOCK_DWORDS * b);
+#pragma unroll
+        for (int q = 0; q < 11; q++) w[q] = (u64)wl[q] | ((u64)wh[q] << 32);
+    }
+#undef P2_PGL_ST
+#else
+    u64 s[12];
+    ZKLC_M u64 get(int i) const { return s[i]; }
+    ZKLC_M void set(int i, u64 x) { s[i] = x; }
+    ZKLC_M void full_round(int layer) { pgl_gate_full_round<false>(s, layer); }
+    ZKLC_M void full_round_init() { pgl_gate_full_round_init<false>(s); }
+    ZKLC_M void partial_block(u64 *w, int b) {      // the linear forms of p2_eval_poseidon_lazy over the PGL_LAZY_* tables
+        u64 z[11], s0 = s[0];
+        for (int q = 0; q < 11; q++) {
+            const u64 sin = w[q];
+            w[q] = gl_sub(s0, sin);
+            z[q] = pgl_sbox_l(sin);
+            gl_acc3 acc;
+            const u32 kq = (11 * b + q) * 3, row = (11 * b + q) * 66;
+            acc.c0 = PGL_LAZY_K[kq] + (u64)(u32)z[q] * 25;
+            acc.c1 = PGL_LAZY_K[kq + 1] + (u64)(u32)(z[q] >> 32) * (25u << 10);      // 2^32 = 2^22 2^10
+            acc.c2 = PGL_LAZY_K[kq + 2];
+            for (int i = 0; i < 11; i++) gl_acc3_mul(acc, s[1 + i], PGL_LAZY_W + row + 6 * i);
+            for (int k = 0; k < q; k++) gl_acc3_mul(acc, z[k], PGL_LAZY_C + row + 6 * k);
+            s0 = gl_acc3_reduce(acc);
+        }
+        s[0] = s0;
+        for (int j = 0; j < 11; j++) {
+            gl_acc3 acc;
+            const u32 kv = (11 * b + j) * 3;
+            acc.c0 = PGL_LAZY_KV[kv] + (u64)(u32)s[1 + j];
+            acc.c1 = PGL_LAZY_KV[kv + 1] + ((u64)(u32)(s[1 + j] >> 32) << 10);
+            acc.c2 = PGL_LAZY_KV[kv + 2];
+            for (int k = 0; k < 11; k++) gl_acc3_mul(acc, z[k], PGL_LAZY_V + (11 * b + j) * 66 + 6 * k);
+            s[1 + j] = gl_acc3_reduce(acc);
+        }
+    }
+#endif
+};
+// poseidon_gate.go:84-181 from generated statements (ZKLC_P2_POSEIDON_GATE=stmt): the structure of p2_eval_poseidon_lazy -- the full
+// rounds are the hash kernel's statements with `computed - wire` and the switch to the wire value between them -- with each lazy
+// partial block ONE statement whose operands are the block's wires, so the partial rounds add one copy of ~3 400 instructions to
+// the kernel instead of 8 000 unrolled compiled ones, and no table pointer lives across a statement.  The constraints are emitted
+// by compiled code between the statements.
+template <class V>
+ZKLC_D void p2_eval_poseidon_stmt(const V &v, p2_consumer &out) {
+    // the head room of the accumulators is checked once for the 123 constraints, not per constraint as p2_consumer::emit does: with
+    // the rounds in a loop the counter is a run-time value, and forty copies of the normalisation were a third of the kernel's code
+    if (out.n + 123 >= 480) {
+        out.n = 0;
+#pragma unroll
+        for (int c = 0; c < P2_MAX_CH; c++) gl_acc3_normalize(out.acc[c]);
+    }
+    out.n += 123;
+    // Both accumulators take every constraint, whatever nch is: eighty wave-uniform branches less, and straight-line code between
+    // the statements.  Every apow[] pointer is a valid table (the prover points the unused ones at the first challenge's), and
+    // result(c) is only read for c < nch.
+    // The alpha powers through two running pointers (four SGPRs across a statement) instead of base + 6 k per constraint.
+    static_assert(P2_MAX_CH == 2, "two challenges");
+    gl_ktab *ap0 = out.apow[0] + 6 * (size_t)out.k, *ap1 = out.apow[1] + 6 * (size_t)out.k;
+    out.k += 123;
+    auto emit = [&](u64 x) {
+        gl_acc3_mul(out.acc[0], x, ap0);
+        gl_acc3_mul(out.acc[1], x, ap1);
+        ap0 += 6;
+        ap1 += 6;
+    };
+    u64 swap = v.w(24);
+    emit(gl_mul(swap, gl_sub(swap, 1)));
+    p2_pgl_state st;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        u64 lhs = v.w(i), rhs = v.w(i + 4), delta = v.w(25 + i);
+        emit(gl_sub(gl_mul(swap, gl_sub(rhs, lhs)), delta));
+        st.set(i, gl_add_lc(gl_add(lhs, delta), PGL_RC[i]));
+        st.set(i + 4, gl_add_lc(gl_sub(rhs, delta), PGL_RC[i + 4]));
+    }
+#pragma unroll
+    for (int i = 8; i < 12; i++) st.set(i, gl_add_lc(v.w(i), PGL_RC[i]));
+    // nine iterations "constraints of this round's S-box inputs, then the round" as in p2_eval_poseidon_lazy; the ninth holds the
+    // permutation's output against the output wires and leaves (one copy of the twelve emissions in the code)
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (int it = 0; it <= 8; it++) {
+        if (it != 0) {
+            const u32 w0 = it == 8 ? 12 : it < 4 ? 29 + 12 * (it - 1) : 87 + 12 * (it - 4);
+            u64 sin[12];
+            p2_load<12>(v, w0, sin);
+#pragma unroll
+            for (int i = 0; i < 12; i++) {
+                emit(gl_sub(st.get(i), sin[i]));
+                st.set(i, sin[i]);
+            }
+        }
+        if (it == 8) break;
+        if (it != 3) {
+            st.full_round(it);
+            continue;
+        }
+        st.full_round_init();
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+        for (int b = 0; b < 2; b++) {
+            u64 w[11];
+            p2_load<11>(v, 65 + 11 * b, w);
+            st.partial_block(w, b);
+#pragma unroll
+            for (int q = 0; q < 11; q++) emit(w[q]);
+        }
+    }
 }
 
 // poseidon_gate.go:84-181, round by round like the default evaluator below but in the LOOSE arithmetic of the C++ permutation

@@ -354,6 +354,74 @@ __global__ void __launch_bounds__(P2_THREADS) p2_quotient_gate_kernel(p2_quotien
         }
 }
 
+// The Poseidon gate from generated statements (TYPE P2_POSEIDON_STMT, ZKLC_P2_POSEIDON_GATE=stmt): what p2_quotient_gate_kernel does,
+// arranged around one fact -- the statements clobber s[32:100], so whatever lives across them has to fit below s32.  Written like the
+// kernel above, the compiler reads every argument it will ever need in the first block and computes all that does not change from
+// gate to gate of the list (135 column addresses, alpha-power pointers at several offsets, the masks of c < nch) in front of the loop,
+// then holds it across the statements in spilled lanes (v_writelane / v_readlane) and scratch.  Here
+//   * the evaluator's inputs are opaque per gate of the list (an empty asm), so nothing of it is computed ahead of the loop;
+//   * everything that is needed AFTER the evaluator -- the gate's record, the selector column, 1 / Z_H, the output -- is read from
+//     the kernel-argument segment again, through a pointer that is opaque at that point, instead of being held since the first block;
+//   * the kernel is held to three waves per SIMD (168 VGPRs: 46 operands and 64 temporaries of the partial block's statement, the two
+//     challenges' accumulators, the sums).
+struct p2_gate_kernargs {      // the argument segment of (p2_quotient_args, p2_gate_list)
+    p2_quotient_args a;
+    p2_gate_list list;
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __attribute__((address_space(4))) const p2_gate_kernargs p2_gate_kernargs_k;
+#define P2_KERNARGS_AGAIN(ka)                                                                 \
+    p2_gate_kernargs_k *ka = (p2_gate_kernargs_k *)__builtin_amdgcn_kernarg_segment_ptr();    \
+    asm volatile("" : "+s"(ka))
+#else
+typedef const p2_gate_kernargs p2_gate_kernargs_k;
+#define P2_KERNARGS_AGAIN(ka) p2_gate_kernargs_k *ka = nullptr      // the host pass only parses the kernel
+#endif
+__global__ void __launch_bounds__(P2_THREADS, 3) p2_quotient_poseidon_stmt_kernel(p2_quotient_args a, p2_gate_list list) {
+    const size_t N = (size_t)1 << a.lde_bits;
+    size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N) return;
+    p2_vars v;
+    v.wires = a.wires;
+    v.consts = nullptr;      // the evaluator reads wires only
+    v.stride = N;
+    v.p = p;
+    v.nsel = 0;
+    for (int k = 0; k < 4; k++) v.pih[k] = 0;
+    p2_consumer out;
+    for (int c = 0; c < P2_MAX_CH; c++) out.apow[c] = (gl_ktab *)a.apow[c];
+    u64 sum[P2_MAX_CH];
+    for (int c = 0; c < P2_MAX_CH; c++) sum[c] = 0;
+    const u32 n_list = list.n;
+#pragma unroll 1
+    for (u32 t = 0; t < n_list; t++) {
+        u32 nch = a.nch;
+        asm volatile("" : "+v"(v.p), "+s"(v.stride), "+s"(nch));
+        out.nch = (int)nch;
+        out.reset(nch + nch * (a.npp + 1));   // the gate constraints follow the Z1 and partial-product terms
+        p2_eval_poseidon_stmt(v, out);
+        P2_KERNARGS_AGAIN(ka);
+        const u32 g = ka->list.idx[t];
+        const p2_gate *rec = ka->a.gates + g;
+        const u64 sel = ka->a.cs[(size_t)rec->selector_index * v.stride + v.p];
+        const u64 f = p2_filter(g, rec->group_start, rec->group_end, sel, ka->a.nsel > 1);
+#pragma unroll
+        for (int c = 0; c < P2_MAX_CH; c++)      // static indices: a dynamic one would push the accumulators into memory
+            if (c < out.nch) sum[c] = gl_add(sum[c], gl_mul(f, out.result(c)));
+    }
+    P2_KERNARGS_AGAIN(kb);
+    const u32 lde_bits = kb->a.lde_bits;
+    const u64 i = __brevll((u64)p) >> (64 - lde_bits);
+    const u64 zi = kb->a.zh_inv[(u32)i & ((1u << kb->a.rate_bits) - 1)];
+    u64 *dst = kb->a.out;
+#pragma unroll
+    for (int c = 0; c < P2_MAX_CH; c++)
+        if (c < (int)kb->a.nch) {
+            u64 *o = dst + (((size_t)c << lde_bits) + p);
+            *o = gl_add(*o, gl_mul(sum[c], zi));
+        }
+}
+
 // ---- all U32AddMany gates of a circuit in ONE evaluator (the Ed25519 circuit has eight variants, 3..16 addends).
 // Every variant keeps 16 + 2 two-bit limbs per operation after its routed wires, and the limb regions of the variants overlap
 // (columns 54..233 of the 234): evaluated gate by gate that is 900 range checks x (x-1)(x-2)(x-3) and 1 476 column loads per LDE
@@ -686,12 +754,15 @@ static bool p2_amt_make_plan(const p2_gate *gates, const p2_gate_list &list, p2_
 
 typedef void (*p2_gate_kernel_fn)(p2_quotient_args, p2_gate_list);
 static p2_gate_kernel_fn p2_gate_kernel_of(u32 type) {
-    // ZKLC_P2_POSEIDON_GATE: the evaluator of the Poseidon gate.  Default (round 5) = `loose`: the plain evaluator's loop structure in
-    // the loose arithmetic of the hash kernel's C++ permutation (2.80 -> 2.53 ms per Ed25519 proof); `plain` = the canonical-value
-    // form that was the default until round 4; `lazy` / `lazy1` = the whole-round / lazy-partial-round forms (plonky2_gates.cuh).
-    // All four give the same field values: tests/test_gpu_plonky2.py proves one circuit under each and compares the bytes.
+    // ZKLC_P2_POSEIDON_GATE: the evaluator of the Poseidon gate.  Default = `stmt` (TYPE P2_POSEIDON_STMT): the full rounds and the
+    // lazy partial blocks from generated statements (2.48 -> 1.33 ms per Ed25519 proof); `loose` = the default
+    // of round 5, the plain evaluator's loop structure in the loose arithmetic of the hash kernel's C++ permutation; `plain` = the
+    // canonical-value form that was the default until round 4; `lazy` / `lazy1` = the whole-round / lazy-partial-round forms in
+    // compiled code (plonky2_gates.cuh).  All five give the same field values: tests/test_gpu_plonky2.py and
+    // tests/test_gpu_poseidon_gate_stmt.py prove circuits under each and compare the bytes.
     static const char *pg = getenv("ZKLC_P2_POSEIDON_GATE");
-    if (type == P2_POSEIDON && (!pg || !pg[0] || !strcmp(pg, "loose"))) return p2_quotient_gate_kernel<P2_POSEIDON_LOOSE>;
+    if (type == P2_POSEIDON && (!pg || !pg[0] || !strcmp(pg, "stmt"))) return p2_quotient_poseidon_stmt_kernel;
+    if (type == P2_POSEIDON && !strcmp(pg, "loose")) return p2_quotient_gate_kernel<P2_POSEIDON_LOOSE>;
     if (type == P2_POSEIDON && pg && !strncmp(pg, "lazy", 4)) {
         // lazy: statements + unrolled partial rounds; lazy1: the partial rounds as rolled loops over per-lane LDS arrays
         return pg[4] == '1' ? p2_quotient_gate_kernel<P2_POSEIDON_LAZY + 1> : p2_quotient_gate_kernel<P2_POSEIDON_LAZY>;
