@@ -53,8 +53,8 @@ def tamper(proof, common, verifier_only, what):
     op = pr["opening_proof"]
     q0 = op["query_round_proofs"][0]
     fp = common["fri_params"]
-    arity = 1 << fp["reduction_arity_bits"][0]
     if what.startswith("step_eval"):
+        arity = 1 << fp["reduction_arity_bits"][0]     # only circuits with a FRI reduction have step evaluations
         ch = V.challenges(V.parse_proof(json.loads(json.dumps(proof)), verifier_only), common)
         within = (ch["query_indices"][0] % (1 << (fp["degree_bits"] + fp["config"]["rate_bits"]))) & (arity - 1)
         pos = within if what == "step_eval_within" else (within + 1) % arity

@@ -1977,7 +1977,10 @@ extern "C" int32_t zklc_plonky2_prove_dev(zklc_ctx *ctx, void *stream, zklc_plon
         a.n_in = ch.n_in;
         a.pow_bits = P.proof_of_work_bits;
         a.found = c->d_found;
-        const u64 batch = 1ULL << (P.proof_of_work_bits + 2 < 24 ? P.proof_of_work_bits + 2 : 24);  // ~98 % hit rate per launch
+        // ~98 % hit rate per launch; never less than one workgroup (5 or fewer bits would round down to a grid of zero blocks).
+        // Every launch scans a whole range [base, base + batch) and keeps its minimum, so the witness is the lowest one
+        const u32 batch_bits = P.proof_of_work_bits + 2 < 24 ? P.proof_of_work_bits + 2 : 24;
+        const u64 batch = (1ULL << batch_bits) > P2_THREADS ? 1ULL << batch_bits : P2_THREADS;
         P2_PIN(c, h_found, unsigned long long, 1);
         unsigned long long found = ~0ULL;
         for (u64 base = 0;; base += batch) {

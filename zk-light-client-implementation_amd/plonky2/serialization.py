@@ -26,16 +26,18 @@ def shapes(common):
     cfg, fp = common["config"], common["fri_params"]
     nch = cfg["num_challenges"]
     routed = cfg["num_routed_wires"]
+    lde_bits = fp["degree_bits"] + fp["config"]["rate_bits"]
     return {
-        "cap": 1 << fp["config"]["cap_height"],
+        # a cap taller than the tree is the tree's leaf level: both provers and the native verifier clamp it the same way
+        "cap": 1 << min(fp["config"]["cap_height"], lde_bits),
         "openings": [("constants", common["num_constants"]), ("plonk_sigmas", routed), ("wires", cfg["num_wires"]),
                      ("plonk_zs", nch), ("plonk_zs_next", nch), ("partial_products", nch * common["num_partial_products"]),
                      ("quotient_polys", nch * common["quotient_degree_factor"])],
         "leaf_widths": [common["num_constants"] + routed, cfg["num_wires"], nch * (1 + common["num_partial_products"]),
                         nch * common["quotient_degree_factor"]],
         "arity_bits": fp["reduction_arity_bits"],
-        "lde_bits": fp["degree_bits"] + fp["config"]["rate_bits"],
-        "cap_height": fp["config"]["cap_height"],
+        "lde_bits": lde_bits,
+        "cap_height": min(fp["config"]["cap_height"], lde_bits),
         "final_len": 1 << (fp["degree_bits"] - sum(fp["reduction_arity_bits"])),
         "rounds": fp["config"]["num_query_rounds"],
     }

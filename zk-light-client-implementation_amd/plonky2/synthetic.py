@@ -375,6 +375,8 @@ def synthetic_circuit(degree_bits, config, mix, num_public_inputs=16, seed=0, fi
     assert budget > 2 * len(mix), "circuit too small for the gate mix"
     total_w = sum(w for _, w in mix)
     counts = [max(2, (budget * w // total_w) & ~1) for _, w in mix]
+    # the two-row minimum per gate type can exceed the budget: the public-input rows and the PublicInputGate row come after the body
+    assert sum(counts) + pi_rows < n, "circuit too small for the gate mix"
     gate_list = [g for g, _ in mix] + [G.PoseidonGate(), G.PublicInputGate(), G.NoopGate()]
     uniq = sorted(set(gate_list), key=lambda g: (g.degree, g.id()))
     index = {g: i for i, g in enumerate(uniq)}
