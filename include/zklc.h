@@ -502,6 +502,25 @@ int32_t zklc_bn254_g1_decode_host(const uint8_t *bytes, uint64_t n, uint32_t fla
 int32_t zklc_bn254_g2_decode_host(const uint8_t *bytes, uint64_t n, uint32_t flags, uint32_t nthreads, uint64_t *words,
                                   uint32_t *status, uint64_t *summary);
 
+/* The writing direction: n points in gnark-crypto's memory layout (words: n x 8 / n x 16 u64, what the decoders above, the
+ * fixed-base multiplications below and `groth16.Setup` leave) -> n slots of the encoding described above, raw or with
+ * ZKLC_POINTS_COMPRESSED, exactly the bytes gnark-crypto's `RawBytes` / `Bytes` give (the point arrays `pk.WriteRawTo` / `pk.WriteTo`
+ * write: util.go:172-216).  An all-zero record is the point at infinity: flag 01, zeros to the full stride.  status[i]:
+ * ZKLC_POINT_OK, ZKLC_POINT_INFINITY, ZKLC_POINT_BAD_ENCODING (a coordinate's words, taken as an integer, are >= p: gnark's memory
+ * form is canonical), and with ZKLC_POINTS_VALIDATE also ZKLC_POINT_NOT_ON_CURVE.  The slot of a rejected record is all 0xFF bytes,
+ * which every decoder above classifies ZKLC_POINT_BAD_ENCODING.  No subgroup test: ZKLC_POINTS_CHECK_SUBGROUP is
+ * ZKLC_ERR_INVALID_ARG here, as ZKLC_POINTS_VALIDATE is for the decoders.  summary, alignment (words and bytes 16 bytes), n <= 2^31
+ * and the meaning of the return value are those of the decoders; the *_dev entries only enqueue (one lane per point). */
+#define ZKLC_POINTS_VALIDATE 4u       /* encode only: test the curve equation */
+int32_t zklc_bn254_g1_encode_dev(zklc_ctx *ctx, void *stream, const uint64_t *d_words, uint64_t n, uint32_t flags, uint8_t *d_bytes,
+                                 uint32_t *d_status, uint64_t *d_summary);
+int32_t zklc_bn254_g2_encode_dev(zklc_ctx *ctx, void *stream, const uint64_t *d_words, uint64_t n, uint32_t flags, uint8_t *d_bytes,
+                                 uint32_t *d_status, uint64_t *d_summary);
+int32_t zklc_bn254_g1_encode_host(const uint64_t *words, uint64_t n, uint32_t flags, uint32_t nthreads, uint8_t *bytes,
+                                  uint32_t *status, uint64_t *summary);
+int32_t zklc_bn254_g2_encode_host(const uint64_t *words, uint64_t n, uint32_t flags, uint32_t nthreads, uint8_t *bytes,
+                                  uint32_t *status, uint64_t *summary);
+
 /* NTT over the BN254 scalar field Fr.  Replaces gnark-crypto `fft.Domain.FFT / FFTInverse` (ecc/bn254/fr/fft, un-vendored)
  * inside `groth16.Prove` (gnark-plonky2-verifier/cmd/web-api.go:77).  data: 2^log_n elements in gnark-crypto's memory layout
  * (x * 2^256 mod r, 4 little-endian u64), transformed in place.  values[k] = sum_j coeffs[j] w^(jk), w = rootOfUnity^(2^28/n);

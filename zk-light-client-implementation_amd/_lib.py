@@ -81,6 +81,10 @@ _SIGS = {
     "zklc_bn254_g2_decode_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     "zklc_bn254_g1_decode_host": (ctypes.c_int32, [_u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     "zklc_bn254_g2_decode_host": (ctypes.c_int32, [_u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    "zklc_bn254_g1_encode_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    "zklc_bn254_g2_encode_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    "zklc_bn254_g1_encode_host": (ctypes.c_int32, [_u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    "zklc_bn254_g2_encode_host": (ctypes.c_int32, [_u8p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     # constraint system (A w, B w, C w)
     "zklc_r1cs_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, _u8p, _u8p, _u8p, ctypes.c_uint64, _u8p,
                                           ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
@@ -174,6 +178,7 @@ _SIGS = {
 NTT_INVERSE, NTT_IN_BITREV, NTT_OUT_BITREV = 1, 2, 4
 POINT_OK, POINT_INFINITY, POINT_BAD_ENCODING, POINT_NOT_ON_CURVE, POINT_NOT_IN_SUBGROUP = range(5)
 POINTS_COMPRESSED, POINTS_CHECK_SUBGROUP = 1, 2
+POINTS_VALIDATE = 4             # encode only
 POINT_CLASS_NAMES = ("OK", "INFINITY", "BAD_ENCODING", "NOT_ON_CURVE", "NOT_IN_SUBGROUP")
 
 _lib = None

@@ -278,6 +278,14 @@ class Context:
         self._check(fn(self._h, _stream_ptr(stream), _dev_ptr(d_bytes), n, flags, _dev_ptr(d_words), _dev_ptr(d_status),
                        _dev_ptr(d_summary)))
 
+    def bn254_points_encode_dev(self, d_words, n, d_bytes, d_status, d_summary, group=1, flags=0, stream=None):
+        """the writing direction: n points in gnark-crypto's memory layout (d_words int64 / uint64 [n, 8], group=2: [n, 16], 16-byte
+        aligned) -> d_bytes, n slots of a key file's point array (flags: _lib.POINTS_COMPRESSED, _lib.POINTS_VALIDATE), d_status
+        uint32 [n], d_summary 4 x u64 as for decoding.  A rejected record's slot is all 0xFF.  Enqueue only."""
+        fn = self._lib.zklc_bn254_g1_encode_dev if group == 1 else self._lib.zklc_bn254_g2_encode_dev
+        self._check(fn(self._h, _stream_ptr(stream), _dev_ptr(d_words), n, flags, _dev_ptr(d_bytes), _dev_ptr(d_status),
+                       _dev_ptr(d_summary)))
+
     def bn254_fr_ntt(self, data, flags=0, coset=0):
         """data: uint64 [n, 4] Fr elements in gnark Montgomery layout -> transformed copy"""
         a = np.ascontiguousarray(data, dtype=np.uint64).reshape(-1, 4).copy()

@@ -60,16 +60,20 @@ ZKLC_HD void gk_load_words(u32 *w, const u32 *src, int nq) {
 }
 
 // gnark-crypto fp.Element.LexicographicallyLargest: the canonical value is above (p - 1) / 2
-ZKLC_HD u32 gk_fp_lex_largest(const fp &y) {
+// (on the canonical value's eight words: the encoder of gnark_points_encode.cuh has them already; then on an element)
+ZKLC_HD u32 gk_words_lex_largest(const u32 *w) {
     const u32 H[8] = {0x6c3e7ea3u, 0x9e10460bu, 0xb438e546u, 0xcbc0b548u, 0x40c0ac2eu, 0xdc2822dbu, 0x7098d014u, 0x18322739u};
-    const u32 one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
-    u32 w[8];
-    fp_freeze_words(w, fp_mul(y, fp_from_words_raw(one)));   // out of the Montgomery domain
     for (int i = 7; i >= 0; i--) {
         if (w[i] > H[i]) return 1;
         if (w[i] < H[i]) return 0;
     }
     return 0;
+}
+ZKLC_HD u32 gk_fp_lex_largest(const fp &y) {
+    const u32 one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+    u32 w[8];
+    fp_freeze_words(w, fp_mul(y, fp_from_words_raw(one)));   // out of the Montgomery domain
+    return gk_words_lex_largest(w);
 }
 // E2.LexicographicallyLargest: A1 decides, A0 only when A1 = 0 (gnark_keys._g2_lex_largest)
 ZKLC_HD u32 gk_fp2_lex_largest(const fp2 &y) { return fp_is_zero(y.c1) ? gk_fp_lex_largest(y.c0) : gk_fp_lex_largest(y.c1); }

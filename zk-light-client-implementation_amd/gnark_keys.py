@@ -15,6 +15,8 @@ trailer and reported, not interpreted.  Tests: round trips and structure only (t
 `load_pk` (end of this module) reads the same layout with the point arrays decoded and validated by the library -- one lane per
 point on the GPU, or the same lane functions on host threads (include/zklc.h zklc_bn254_g{1,2}_decode_{dev,host}) -- so that the
 reader is not the bottleneck of a start-up; it pins nothing: read_g1 / read_g2 below stay the specification of those kernels.
+`save_pk` / `save_vk` are the writing direction (zklc_bn254_g{1,2}_encode_{dev,host}): a key in that memory layout, as `Setup` or
+`load_pk` leave it, to the file; write_g1 / write_g2 and pk_to_gnark_bytes / vk_to_gnark_bytes stay their specification.
 """
 import struct
 
@@ -487,3 +489,309 @@ def load_pk(src, n_public, raw=True, ctx=None, check_subgroup=True, nthreads=0, 
             words = words[:n - 1]
         pk[name + ("_words" if ctx is None else "_dev")] = words
     return pk
+
+
+# ---------------------------------------------------------------------------------------------- batched encoding (C ABI)
+# include/zklc.h zklc_bn254_g{1,2}_encode_{dev,host}: the writing direction.  The point arrays of a key in gnark-crypto's memory
+# layout (what load_pk, groth16_setup.KeySetup and setup_host leave) become the bytes of a key file without a Python integer per
+# point; write_g1 / write_g2 on words_to_points stay the specification of those kernels.
+def _encode_flags(compressed, validate):
+    from . import _lib
+    return (_lib.POINTS_COMPRESSED if compressed else 0) | (_lib.POINTS_VALIDATE if validate else 0)
+
+
+def _encode_chunks_host(words, n, g2, flags, nthreads, chunk_points):
+    """the host entry over `words` (uint64 / int64 [n, 8 | 16]) chunk by chunk -> yields (offset, count, bytes, status, summary):
+    views of buffers that the next step overwrites"""
+    from . import _lib
+    lib = _lib.load()
+    fn = lib.zklc_bn254_g2_encode_host if g2 else lib.zklc_bn254_g1_encode_host
+    stride, width = _stride(g2, bool(flags & _lib.POINTS_COMPRESSED)), 16 if g2 else 8
+    src = np.ascontiguousarray(words).view(np.uint64).reshape(-1, width)
+    if src.shape[0] < n:
+        raise ValueError("point array too short")
+    cap = min(max(n, 1), chunk_points)
+    out, status, summary = _aligned_u8(cap * stride), np.zeros(cap, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
+    stage = None
+    for off in range(0, max(n, 1), chunk_points):
+        k = min(chunk_points, n - off)
+        part = src[off:off + k]
+        if k and part.ctypes.data % 16:                                   # a slice of the caller's array at an odd address
+            if stage is None:
+                stage = _aligned_u8(cap * width * 8).view(np.uint64).reshape(cap, width)
+            stage[:k] = part
+            part = stage[:k]
+        rc = fn(part.ctypes.data if k else None, k, flags, nthreads, out.ctypes.data, status.ctypes.data, summary.ctypes.data)
+        if rc != 0:
+            raise _lib.ZklcError(rc)
+        yield off, k, out[:k * stride], status[:k], summary
+
+
+def encode_points_host(words, n, g2=False, compressed=False, validate=False, nthreads=0, chunk_points=_CHUNK_POINTS):
+    """n points in gnark-crypto's memory layout (uint64 [n, 8 | 16]) on host threads (0 = 16), no GPU -> (bytes uint8 [n x stride]:
+    the slots of a key file's point array, status uint32 [n], summary [OK, infinity, rejected, first rejected index | None]).  The
+    slot of a rejected record is all 0xFF."""
+    stride = _stride(g2, compressed)
+    data, status, total = np.empty(n * stride, dtype=np.uint8), np.zeros(n, dtype=np.uint32), [0, 0, 0, None]
+    for off, k, part, st, summary in _encode_chunks_host(words, n, g2, _encode_flags(compressed, validate), nthreads, chunk_points):
+        data[off * stride:(off + k) * stride] = part
+        status[off:off + k] = st
+        _add_summary(total, summary, off)
+    return data, status, total
+
+
+def _device_words(ctx, words, width):
+    """a key's point array as a contiguous, 16-byte aligned int64 device tensor [n, width] on ctx's GPU (a host array is uploaded)"""
+    import torch
+    dev = torch.device("cuda", ctx.device_id)
+    if not isinstance(words, torch.Tensor):
+        words = torch.from_numpy(np.ascontiguousarray(words).view(np.int64).reshape(-1, width))
+    t = words.to(dev).reshape(-1, width).contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone()
+    return t
+
+
+def encode_points_dev(ctx, words, n, g2=False, compressed=False, validate=False, chunk_points=_CHUNK_POINTS):
+    """the same on ctx's GPU.  words: an int64 device tensor [n, 8 | 16] (a host array is uploaded first)
+    -> (bytes: torch uint8 [n x stride] on the device, status: torch int32 [n] on the device, summary as encode_points_host)"""
+    import torch
+    flags = _encode_flags(compressed, validate)
+    stride, width = _stride(g2, compressed), 16 if g2 else 8
+    dev = torch.device("cuda", ctx.device_id)
+    src = _device_words(ctx, words, width)
+    if src.shape[0] < n:
+        raise ValueError("point array too short")
+    data = torch.zeros(n * stride, dtype=torch.uint8, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_summary = torch.zeros(4, dtype=torch.int64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()                       # torch fills on ITS stream; the kernels run on the context's
+    total = [0, 0, 0, None]
+    for off in range(0, max(n, 1), chunk_points):
+        k = min(chunk_points, n - off)
+        ctx.bn254_points_encode_dev(src.data_ptr() + off * width * 8, k, data.data_ptr() + off * stride, status.data_ptr() + off * 4,
+                                    d_summary, group=2 if g2 else 1, flags=flags, stream=ctx.stream_ptr())
+        ctx.synchronize()
+        _add_summary(total, d_summary.cpu().numpy().view(np.uint64), off)
+    return data, status, total
+
+
+def _rejected(name, index, cls):
+    from . import _lib
+    return ProofInvalid("%s[%d]: %s" % (name, index, _lib.POINT_CLASS_NAMES[int(cls)]))
+
+
+def _tick(stats, key, t0):
+    import time
+    if stats is not None:
+        stats[key] = stats.get(key, 0.0) + time.perf_counter() - t0
+
+
+class _HostPointWriter:
+    """point arrays through the host encoder into a file, chunk by chunk"""
+
+    def __init__(self, raw, validate, nthreads, chunk_points, stats):
+        self.flags, self.nthreads, self.chunk, self.stats = _encode_flags(not raw, validate), nthreads, chunk_points, stats
+
+    def words(self, a, width):
+        if not isinstance(a, np.ndarray):                                 # a device tensor of a key made or loaded on a GPU
+            a = a.cpu().numpy()
+        return np.ascontiguousarray(a).view(np.uint64).reshape(-1, width)
+
+    def write(self, f, name, words, g2):
+        import time
+        n, total = words.shape[0], 0
+        if not n:
+            return 0
+        chunks = _encode_chunks_host(words, n, g2, self.flags, self.nthreads, self.chunk)
+        while True:
+            t = time.perf_counter()
+            step = next(chunks, None)
+            _tick(self.stats, "encode_s", t)
+            if step is None:
+                return total
+            off, k, part, status, summary = step
+            if int(summary[2]):
+                raise _rejected(name, off + int(summary[3]), status[int(summary[3])])
+            t = time.perf_counter()
+            f.write(part)
+            _tick(self.stats, "write_s", t)
+            total += part.size
+
+    def close(self):
+        pass
+
+
+class _DevicePointWriter:
+    """point arrays through the kernels into a file: two device buffers and two page-locked staging buffers, so that the write of
+    chunk j runs while chunk j + 1 is encoded and read back.  Every read-back is enqueued after a wait for the context's stream
+    (the ordering rule of zklc_readback_async: no copy parked in a DMA queue behind unfinished kernels)."""
+
+    def __init__(self, ctx, raw, validate, chunk_points, stats):
+        import torch
+        self.ctx, self.flags, self.chunk, self.stats = ctx, _encode_flags(not raw, validate), chunk_points, stats
+        self.compressed = not raw
+        self.dev = torch.device("cuda", ctx.device_id)
+        self.stream = torch.cuda.ExternalStream(ctx.stream_ptr(), device=self.dev)
+        self.cap = 0
+
+    def _reserve(self, nbytes, points):
+        import torch
+        if nbytes <= self.cap:
+            return
+        self.cap = nbytes
+        self.d_out = [torch.empty(nbytes, dtype=torch.uint8, device=self.dev) for _ in range(2)]
+        self.pinned = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.d_status = [torch.empty(points, dtype=torch.int32, device=self.dev) for _ in range(2)]
+        self.d_summary = [torch.zeros(4, dtype=torch.int64, device=self.dev) for _ in range(2)]
+        torch.cuda.current_stream(self.dev).synchronize()               # torch hands blocks out on ITS stream
+
+    def words(self, a, width):
+        return _device_words(self.ctx, a, width)
+
+    def write(self, f, name, words, g2):
+        import time
+        import torch
+        ctx, n = self.ctx, words.shape[0]
+        if not n:
+            return 0
+        stride, width = _stride(g2, self.compressed), 16 if g2 else 8
+        step = min(n, self.chunk)
+        self._reserve(step * (128 if not self.compressed else 64), step)
+        torch.cuda.current_stream(self.dev).synchronize()               # `words` may have been made on torch's stream
+        m = (n + step - 1) // step
+        count = lambda j: min(step, n - j * step)
+
+        def launch(j):
+            ctx.bn254_points_encode_dev(words.data_ptr() + j * step * width * 8, count(j), self.d_out[j & 1], self.d_status[j & 1],
+                                        self.d_summary[j & 1], group=2 if g2 else 1, flags=self.flags, stream=ctx.stream_ptr())
+
+        def put(j):
+            t = time.perf_counter()
+            f.write(self.pinned[j & 1].numpy()[:count(j) * stride])
+            _tick(self.stats, "write_s", t)
+
+        launch(0)
+        for j in range(m):
+            t = time.perf_counter()
+            ctx.synchronize()                                           # settled: kernel j has run, read-back j - 1 has landed
+            summary = self.d_summary[j & 1].cpu().numpy().view(np.uint64)
+            _tick(self.stats, "device_wait_s", t)
+            if int(summary[2]):
+                i = int(summary[3])
+                raise _rejected(name, j * step + i, self.d_status[j & 1][i].item())
+            nb = count(j) * stride
+            with torch.cuda.stream(self.stream):
+                self.pinned[j & 1][:nb].copy_(self.d_out[j & 1][:nb], non_blocking=True)
+            if j + 1 < m:
+                launch(j + 1)
+            if j:
+                put(j - 1)
+        t = time.perf_counter()
+        ctx.synchronize()
+        _tick(self.stats, "device_wait_s", t)
+        put(m - 1)
+        return n * stride
+
+    def close(self):
+        self.ctx.synchronize()
+
+
+def _key_words(wr, key, name, g2):
+    """the point array `name` of a key dictionary, whichever form it has: <name>_dev (device tensor), <name>_words (numpy) or a list
+    of integer tuples under <name>"""
+    width = 16 if g2 else 8
+    for suffix in ("_dev", "_words"):
+        if name + suffix in key:
+            return wr.words(key[name + suffix], width)
+    return wr.words(points_to_words(list(key[name]), g2=g2), width)
+
+
+def _key_single(wr, key, name, g2):
+    width = 16 if g2 else 8
+    if name + "_words" in key:
+        return wr.words(np.ascontiguousarray(key[name + "_words"]).reshape(1, width), width)
+    return wr.words(points_to_words([key[name]], g2=g2), width)
+
+
+def _open_dst(dst):
+    import os
+    if isinstance(dst, (str, os.PathLike)):
+        return open(dst, "wb"), True
+    return dst, False
+
+
+def _save(dst, body):
+    """runs body(f) -> bytes written; a file this call created is removed when the body raises"""
+    import os
+    f, is_path = _open_dst(dst)
+    try:
+        total = body(f)
+    except BaseException:
+        if is_path:
+            f.close()
+            os.remove(dst)
+        raise
+    if is_path:
+        f.close()
+    return total
+
+
+def _point_writer(raw, ctx, validate, nthreads, chunk_points, stats):
+    if chunk_points < 1:
+        raise ValueError("chunk_points must be positive")
+    if ctx is None:
+        return _HostPointWriter(raw, validate, nthreads, chunk_points, stats)
+    return _DevicePointWriter(ctx, raw, validate, chunk_points, stats)
+
+
+def save_pk(pk, dst, raw=True, ctx=None, validate=True, nthreads=0, chunk_points=_CHUNK_POINTS, trailer=b"", stats=None):
+    """pk.bin in the layout of pk_to_gnark_bytes, the point arrays encoded by the library and written as they arrive: the file
+    never exists as one Python object.  dst: a path or a binary file object -> the number of bytes written.  pk: the dictionary of
+    `KeySetup.run` / `load_pk(ctx)` (`*_dev` tensors) or of `setup_host` / `load_pk(ctx=None)` (`*_words` arrays), A / B1 / B2
+    compacted with infinity_a / infinity_b; the five single points as `<name>_words` or integer tuples under `<name>`.  ctx=None: host threads; with a
+    Context: on its GPU.  validate: every point is tested against its curve equation.  A rejected point raises ProofInvalid with
+    the array, the index and the class, in load_pk's wording; a file this call opened is removed.  stats: a dictionary that
+    receives the seconds spent waiting for the encoder and writing."""
+    def body(f):
+        put = lambda b: (f.write(b), len(b))[1]
+        wr = _point_writer(raw, ctx, validate, nthreads, chunk_points, stats)
+        try:
+            arrays = {name: _key_words(wr, pk, name, name == "B2") for name in ("A", "B1", "Z", "K", "B2")}
+            inf_a, inf_b = np.asarray(pk["infinity_a"]).astype(bool), np.asarray(pk["infinity_b"]).astype(bool)
+            total = put(_domain_bytes(int(pk["n"])))
+            for name in ("alpha1", "beta1", "delta1"):
+                total += wr.write(f, name, _key_single(wr, pk, name, False), False)
+            for name in ("A", "B1", "Z", "K"):
+                total += put(struct.pack(">I", arrays[name].shape[0]))
+                total += wr.write(f, name, arrays[name], False)
+            for name in ("beta2", "delta2"):
+                total += wr.write(f, name, _key_single(wr, pk, name, True), True)
+            total += put(struct.pack(">I", arrays["B2"].shape[0]))
+            total += wr.write(f, "B2", arrays["B2"], True)
+            total += put(struct.pack(">QQQ", len(inf_a), int(inf_a.sum()), int(inf_b.sum())))
+            total += put(inf_a.astype(np.uint8).tobytes()) + put(inf_b.astype(np.uint8).tobytes())
+            return total + put(bytes(trailer))
+        finally:
+            wr.close()
+    return _save(dst, body)
+
+
+def save_vk(vk, dst, raw=True, ctx=None, validate=True, nthreads=0, chunk_points=_CHUNK_POINTS, trailer=b""):
+    """vk.bin in the layout of vk_to_gnark_bytes, every point through the library's encoder.  vk: the integer-tuple dictionary of
+    `Setup` (converted with points_to_words: a verifying key is small); `<name>_words` and K_words / K_dev are taken as they are.
+    Otherwise as save_pk."""
+    def body(f):
+        put = lambda b: (f.write(b), len(b))[1]
+        wr = _point_writer(raw, ctx, validate, nthreads, chunk_points, None)
+        try:
+            total = 0
+            for name, g2 in (("alpha1", False), ("beta1", False), ("beta2", True), ("gamma2", True), ("delta1", False), ("delta2", True)):
+                total += wr.write(f, name, _key_single(wr, vk, name, g2), g2)
+            k = _key_words(wr, vk, "K", False)
+            total += put(struct.pack(">I", k.shape[0]))
+            total += wr.write(f, "K", k, False)
+            return total + put(bytes(trailer))
+        finally:
+            wr.close()
+    return _save(dst, body)

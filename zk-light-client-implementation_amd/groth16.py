@@ -559,3 +559,17 @@ class NativeGroth16Verifier:
 
 # ---------------------------------------------------------------------------------------------- groth16.Setup (zklc_amd/groth16_setup.py)
 from .groth16_setup import KeySetup, Setup, setup_host, setup_scalars_dev, setup_scalars_host  # noqa: E402,F401
+
+
+# ---------------------------------------------------------------------------------------------- key files (zklc_amd/gnark_keys.py)
+# (gnark_keys imports this module for fp_to_mont_words, so its two writers are bound when they are called)
+def save_pk(pk, dst, **kw):
+    """`pk.WriteRawTo` / `pk.WriteTo` for the proving key of `Setup`: gnark_keys.save_pk"""
+    from .gnark_keys import save_pk as f
+    return f(pk, dst, **kw)
+
+
+def save_vk(vk, dst, **kw):
+    """`vk.WriteRawTo` / `vk.WriteTo` for the verifying key of `Setup`: gnark_keys.save_vk"""
+    from .gnark_keys import save_vk as f
+    return f(vk, dst, **kw)
