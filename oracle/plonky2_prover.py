@@ -62,17 +62,19 @@ class Tree:
 class Batch:
     """PolynomialBatch: coefficients, LDE values on g*<w_N> and the Merkle tree over bit-reversed rows"""
 
-    def __init__(self, H, coeffs, rate_bits, cap_height):
+    def __init__(self, H, coeffs, rate_bits, cap_height, leaf_hook=None):
         self.coeffs = coeffs
         self.lde = [gl.coset_lde(c, rate_bits) for c in coeffs]      # natural order
         N = len(self.lde[0])
         bits = N.bit_length() - 1
         self.leaves = [[p[gl.bitrev(i, bits)] for p in self.lde] for i in range(N)]
+        if leaf_hook is not None:        # a dishonest prover: the committed leaves differ from the LDE of the coefficients
+            self.leaves = leaf_hook(self.leaves) or self.leaves
         self.tree = Tree(H, self.leaves, cap_height)
 
     @classmethod
-    def from_values(cls, H, values, rate_bits, cap_height):
-        return cls(H, [gl.ntt(v, inverse=True) for v in values], rate_bits, cap_height)
+    def from_values(cls, H, values, rate_bits, cap_height, leaf_hook=None):
+        return cls(H, [gl.ntt(v, inverse=True) for v in values], rate_bits, cap_height, leaf_hook)
 
 
 def eval_poly_ext(coeffs, x):
@@ -97,7 +99,19 @@ def preprocess(common, constants, sigmas, H):
     return batch, digest
 
 
-def prove(common, constants, sigmas, wires, public_inputs, H=V.HasherGL, cs_batch=None, digest=None, trace=None):
+def prove(common, constants, sigmas, wires, public_inputs, H=V.HasherGL, cs_batch=None, digest=None, trace=None, hooks=None):
+    """hooks: None (the honest prover), or a dict of callables that make a DISHONEST prover for the verifier's tests.  Each one
+    changes a value before it is committed or observed, so the Merkle paths, the transcript and the proof of work of the
+    resulting proof are honest for the changed data:
+      "leaves"(name, leaves)      name in "wires" / "zs_pp" / "quotient"; leaves[x_index][column] as committed (bit-reversed row
+                                  order).  The coefficients, and so the openings and every later layer, stay honest.
+      "fri_layer"(i, cosets)      cosets[coset index][position] = (a, b): the values of FRI layer i before its tree is built
+      "final_poly"(coeffs)        the final polynomial before it is observed
+      "pow_witness"(candidates)   candidates yields (witness, query indices that follow from it) for every valid witness in
+                                  increasing order; returns the witness to use
+    The first three change their argument in place or return a replacement."""
+    hk = hooks or {}
+    leaf_hook = lambda name: (lambda leaves: hk["leaves"](name, leaves)) if "leaves" in hk else None
     cfg, fp = common["config"], common["fri_params"]
     fc = fp["config"]
     rate_bits, cap_h = fc["rate_bits"], fc["cap_height"]
@@ -119,7 +133,7 @@ def prove(common, constants, sigmas, wires, public_inputs, H=V.HasherGL, cs_batc
     ch = V.Challenger(H)
     ch.observe_hash(digest)
     ch.observe_many(pih)
-    wires_b = Batch.from_values(H, wires, rate_bits, cap_h)
+    wires_b = Batch.from_values(H, wires, rate_bits, cap_h, leaf_hook("wires"))
     ch.observe_cap(wires_b.tree.cap)
     betas, gammas = ch.challenges(nch), ch.challenges(nch)
     tr["betas"], tr["gammas"] = betas, gammas
@@ -148,7 +162,7 @@ def prove(common, constants, sigmas, wires, public_inputs, H=V.HasherGL, cs_batc
         assert zx == 1, "copy constraints are not satisfied by the witness (Z does not close)"
         zs.append(z)
         pps.append(pp)
-    zs_pp_b = Batch.from_values(H, zs + [p for pp in pps for p in pp], rate_bits, cap_h)
+    zs_pp_b = Batch.from_values(H, zs + [p for pp in pps for p in pp], rate_bits, cap_h, leaf_hook("zs_pp"))
     ch.observe_cap(zs_pp_b.tree.cap)
     alphas = ch.challenges(nch)
     tr["alphas"] = alphas
@@ -183,7 +197,7 @@ def prove(common, constants, sigmas, wires, public_inputs, H=V.HasherGL, cs_batc
         assert all(v == 0 for v in co[qdf * n:])
         for k in range(qdf):
             chunks.append(co[k * n:(k + 1) * n])
-    quot_b = Batch(H, chunks, rate_bits, cap_h)
+    quot_b = Batch(H, chunks, rate_bits, cap_h, leaf_hook("quotient"))
     ch.observe_cap(quot_b.tree.cap)
     zeta = ch.ext_challenge()
     tr["zeta"] = zeta
@@ -225,13 +239,17 @@ def prove(common, constants, sigmas, wires, public_inputs, H=V.HasherGL, cs_batc
     values = ext_coset_fft(coeffs, gl.GENERATOR)
     shift = gl.GENERATOR
     trees, fri_betas = [], []
+    tr["fri_betas"] = fri_betas          # grows with the layers: a "fri_layer" hook of layer i sees the betas of the layers before
     for arity_bits in fp["reduction_arity_bits"]:
         arity = 1 << arity_bits
         rv = bitrev_list(values)
-        leaves = [[c for e in rv[k:k + arity] for c in e] for k in range(0, len(rv), arity)]
+        chunked = [rv[k:k + arity] for k in range(0, len(rv), arity)]
+        if "fri_layer" in hk:
+            chunked = hk["fri_layer"](len(trees), chunked) or chunked
+        leaves = [[c for e in coset for c in e] for coset in chunked]
         t = Tree(H, leaves, cap_h)
         ch.observe_cap(t.cap)
-        trees.append((t, [rv[k:k + arity] for k in range(0, len(rv), arity)]))
+        trees.append((t, chunked))
         beta = ch.ext_challenge()
         fri_betas.append(beta)
         coeffs = [V.reduce_with_powers(coeffs[k:k + arity], beta) for k in range(0, len(coeffs), arity)]
@@ -239,21 +257,36 @@ def prove(common, constants, sigmas, wires, public_inputs, H=V.HasherGL, cs_batc
         values = ext_coset_fft(coeffs, shift)
     assert all(c == (0, 0) for c in coeffs[len(coeffs) >> rate_bits:])
     final_poly = coeffs[:len(coeffs) >> rate_bits]
+    if "final_poly" in hk:
+        final_poly = hk["final_poly"](final_poly) or final_poly
     for c in final_poly:
         ch.observe_ext(c)
     # proof of work: lowest witness whose response has pow_bits leading zeros
     pow_bits = fc["proof_of_work_bits"]
     base_state, base_inp = list(ch.state), list(ch.inp)
-    witness = 0
-    while True:
-        st = list(base_state)
-        inp = base_inp + [witness]
-        for i, e in enumerate(inp):
-            st[i] = e
-        st = pgl._perm(st)
-        if st[7] < (1 << (64 - pow_bits)):
-            break
-        witness += 1
+
+    def valid_witnesses():
+        witness = 0
+        while True:
+            st = list(base_state)
+            inp = base_inp + [witness]
+            for i, e in enumerate(inp):
+                st[i] = e
+            st = pgl._perm(st)
+            if st[7] < (1 << (64 - pow_bits)):
+                yield witness
+            witness += 1
+
+    def query_indices(witness):
+        c2 = V.Challenger(H)
+        c2.state, c2.inp, c2.out = list(ch.state), list(ch.inp), list(ch.out)
+        c2.observe(witness)
+        c2.challenge()
+        return [c2.challenge() % N for _ in range(fc["num_query_rounds"])]
+    if "pow_witness" in hk:
+        witness = hk["pow_witness"]((w, query_indices(w)) for w in valid_witnesses())
+    else:
+        witness = next(valid_witnesses())
     ch.observe(witness)
     resp = ch.challenge()
     assert resp < (1 << (64 - pow_bits))

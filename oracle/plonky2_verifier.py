@@ -214,6 +214,32 @@ def check_vanishing(pf, common, ch):
         assert van == gl.ext_mul(zh, t), "vanishing polynomial identity, challenge %d" % i
 
 
+def subgroup_x(x_index, n_log):
+    """x = g_mult * w^(bitrev(x_index)) (fri.go:187-206)"""
+    rev = int(format(x_index, "0%db" % n_log)[::-1], 2)
+    return gl.GENERATOR * pow(gl.root_of_unity(n_log), rev, P) % P
+
+
+def interpolate_coset(evals, x, within, arity_bits, beta):
+    """the coset's evaluations (bit-reversed order; x is the point of position `within`) interpolated at beta (fri.go:314-384)"""
+    arity = 1 << arity_bits
+    gk = gl.root_of_unity(arity_bits)
+    rev_within = int(format(within, "0%db" % arity_bits)[::-1], 2)
+    start = pow(gl.inv(gk), rev_within, P) * x % P
+    xs = [(start * pow(gk, j, P) % P, 0) for j in range(arity)]
+    ys = [None] * arity
+    for j in range(arity):
+        ys[int(format(j, "0%db" % arity_bits)[::-1], 2)] = evals[j]
+    acc = (0, 0)
+    for a in range(arity):
+        term = ys[a]
+        for b2 in range(arity):
+            if a != b2:
+                term = gl.ext_mul(term, gl.ext_mul(gl.ext_sub(beta, xs[b2]), gl.ext_inv(gl.ext_sub(xs[a], xs[b2]))))
+        acc = gl.ext_add(acc, term)
+    return acc
+
+
 def verify(proof_json, verifier_json, common, max_rounds=None):
     """Returns the derived challenges; raises AssertionError on any failed check."""
     pf = parse_proof(proof_json, verifier_json)
@@ -250,9 +276,7 @@ def verify(proof_json, verifier_json, common, max_rounds=None):
             leaf, sib = init[k]
             assert len(leaf) == widths[k] and len(sib) == n_log - cap_h
             assert merkle_verify(pf["hasher"], leaf, x_index, sib, caps[k]), "initial tree %d, round %d" % (k, rnd)
-        # x = g_mult * w^(bitrev(x_index)) (fri.go:187-206)
-        rev = int(format(x_index, "0%db" % n_log)[::-1], 2)
-        x = gl.GENERATOR * pow(gl.root_of_unity(n_log), rev, P) % P
+        x = subgroup_x(x_index, n_log)
         # combine (fri.go:208-251)
         s = (0, 0)
         for b in range(2):
@@ -270,23 +294,7 @@ def verify(proof_json, verifier_json, common, max_rounds=None):
             arity = 1 << arity_bits
             within, coset = idx & (arity - 1), idx >> arity_bits
             assert evals[within] == old, "fri consistency, round %d step %d" % (rnd, i)
-            # interpolate the coset evaluations at beta (fri.go:314-384)
-            gk = gl.root_of_unity(arity_bits)
-            rev_within = int(format(within, "0%db" % arity_bits)[::-1], 2)
-            start = pow(gl.inv(gk), rev_within, P) * x % P
-            xs = [(start * pow(gk, j, P) % P, 0) for j in range(arity)]
-            ys = [None] * arity
-            for j in range(arity):
-                ys[int(format(j, "0%db" % arity_bits)[::-1], 2)] = evals[j]
-            beta = ch["fri_betas"][i]
-            acc = (0, 0)
-            for a in range(arity):
-                term = ys[a]
-                for b2 in range(arity):
-                    if a != b2:
-                        term = gl.ext_mul(term, gl.ext_mul(gl.ext_sub(beta, xs[b2]), gl.ext_inv(gl.ext_sub(xs[a], xs[b2]))))
-                acc = gl.ext_add(acc, term)
-            old = acc
+            old = interpolate_coset(evals, x, within, arity_bits, ch["fri_betas"][i])
             flat = [c for e in evals for c in e]
             bits -= arity_bits
             assert len(sib) == bits - cap_h
