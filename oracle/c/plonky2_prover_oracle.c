@@ -186,6 +186,31 @@ static void two_to_one(const u64 *l, const u64 *r, u64 *out4) {
     memcpy(out4, s, 32);
 }
 
+/* ------------------------------------------------------------------------------------------------ the configuration's hasher
+ * hasher 0: Poseidon-Goldilocks (above), 1: Poseidon-BN128 (poseidon_bn254_oracle.c; a digest is one Fr in 4 little-endian
+ * words).  What oracle/plonky2_prover.py does with `H`: the Merkle trees, the circuit digest, `to_vec` where a digest is
+ * observed.  The public-input hash, the challenger's permutation and the proof of work stay Poseidon-Goldilocks. */
+int zklc_oracle_pbn_ready(void);
+void zklc_oracle_pbn_hash_no_pad(const u64 *in, u64 stride, u64 len, u64 *out4);
+void zklc_oracle_pbn_hash_or_noop(const u64 *in, u64 stride, u64 len, u64 *out4);
+void zklc_oracle_pbn_two_to_one(const u64 *l, const u64 *r, u64 *out4);
+void zklc_oracle_pbn_to_vec(const u64 *h4, u64 *out5);
+static void h_hash_no_pad(int hasher, const u64 *in, u64 len, u64 *out4) {
+    if (hasher) zklc_oracle_pbn_hash_no_pad(in, 1, len, out4); else hash_no_pad(in, len, out4);
+}
+static void h_hash_or_noop(int hasher, const u64 *in, u64 len, u64 *out4) {
+    if (hasher) zklc_oracle_pbn_hash_or_noop(in, 1, len, out4); else hash_or_noop(in, len, out4);
+}
+static void h_two_to_one(int hasher, const u64 *l, const u64 *r, u64 *out4) {
+    if (hasher) zklc_oracle_pbn_two_to_one(l, r, out4); else two_to_one(l, r, out4);
+}
+/* digest -> the elements that are observed and hashed: 4 (itself) or 5 (7-byte chunks); -> their number */
+static int h_to_vec(int hasher, const u64 *h4, u64 *out) {
+    if (hasher) { zklc_oracle_pbn_to_vec(h4, out); return 5; }
+    memcpy(out, h4, 32);
+    return 4;
+}
+
 /* ------------------------------------------------------------------------------------------------ Merkle tree */
 typedef struct {
     int log_leaves, cap_height;
@@ -196,19 +221,19 @@ static u64 *tree_level(const tree_t *t, int l) {      /* l = 0: leaf digests */
     for (int k = 0; k < l; k++) off += 4ULL << (t->log_leaves - k);
     return t->digests + off;
 }
-static void tree_build(tree_t *t, const u64 *leaves, u64 width, int log_leaves, int cap_height) {
+static void tree_build(tree_t *t, int hasher, const u64 *leaves, u64 width, int log_leaves, int cap_height) {
     if (cap_height > log_leaves) cap_height = log_leaves;
     t->log_leaves = log_leaves;
     t->cap_height = cap_height;
     u64 n = 1ULL << log_leaves;
     t->digests = malloc(8 * n * 8);
 #pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < (int64_t)n; i++) hash_or_noop(leaves + (u64)i * width, width, t->digests + 4 * i);
+    for (int64_t i = 0; i < (int64_t)n; i++) h_hash_or_noop(hasher, leaves + (u64)i * width, width, t->digests + 4 * i);
     for (int l = 0; l < log_leaves - cap_height; l++) {
         u64 *lev = tree_level(t, l), *nxt = tree_level(t, l + 1);
         u64 parents = n >> (l + 1);
 #pragma omp parallel for schedule(static)
-        for (int64_t i = 0; i < (int64_t)parents; i++) two_to_one(lev + 8 * i, lev + 8 * i + 4, nxt + 4 * i);
+        for (int64_t i = 0; i < (int64_t)parents; i++) h_two_to_one(hasher, lev + 8 * i, lev + 8 * i + 4, nxt + 4 * i);
     }
 }
 static const u64 *tree_cap(const tree_t *t) { return tree_level(t, t->log_leaves - t->cap_height); }
@@ -222,7 +247,8 @@ typedef struct {
     u64 *leaves;   /* [N][width], leaf i = the values at natural index bitrev(i) */
     tree_t tree;
 } batch_t;
-static void batch_from_coeffs(batch_t *b, u64 *coeffs /* owned */, u32 width, int degree_bits, int rate_bits, int cap_height) {
+static void batch_from_coeffs(batch_t *b, int hasher, u64 *coeffs /* owned */, u32 width, int degree_bits, int rate_bits,
+                              int cap_height) {
     b->width = width;
     b->n = 1ULL << degree_bits;
     b->N = b->n << rate_bits;
@@ -236,14 +262,14 @@ static void batch_from_coeffs(batch_t *b, u64 *coeffs /* owned */, u32 width, in
         u64 src = bitrev((u64)i, bits);
         for (u32 k = 0; k < width; k++) b->leaves[(u64)i * width + k] = b->lde[(u64)k * b->N + src];
     }
-    tree_build(&b->tree, b->leaves, width, bits, cap_height);
+    tree_build(&b->tree, hasher, b->leaves, width, bits, cap_height);
 }
-static void batch_from_values(batch_t *b, const u64 *values, u32 width, int degree_bits, int rate_bits, int cap_height) {
+static void batch_from_values(batch_t *b, int hasher, const u64 *values, u32 width, int degree_bits, int rate_bits, int cap_height) {
     u64 n = 1ULL << degree_bits;
     u64 *c = malloc((u64)width * n * 8);
     memcpy(c, values, (u64)width * n * 8);
     ntt_batch(c, degree_bits, width, 1);
-    batch_from_coeffs(b, c, width, degree_bits, rate_bits, cap_height);
+    batch_from_coeffs(b, hasher, c, width, degree_bits, rate_bits, cap_height);
 }
 static void batch_free(batch_t *b) { free(b->coeffs); free(b->lde); free(b->leaves); free(b->tree.digests); memset(b, 0, sizeof *b); }
 
@@ -263,6 +289,10 @@ static void ch_observe(chal_t *c, u64 e) {
 }
 static void ch_observe_many(chal_t *c, const u64 *e, u64 n) { for (u64 i = 0; i < n; i++) ch_observe(c, e[i]); }
 static void ch_observe_ext(chal_t *c, e2 x) { ch_observe(c, x.a); ch_observe(c, x.b); }
+static void ch_observe_hashes(chal_t *c, int hasher, const u64 *h, u64 count) {
+    u64 v[5];
+    for (u64 i = 0; i < count; i++) ch_observe_many(c, v, (u64)h_to_vec(hasher, h + 4 * i, v));
+}
 static u64 ch_challenge(chal_t *c) {
     if (c->n_in || !c->n_out) ch_duplex(c);
     return c->out[--c->n_out];
@@ -629,7 +659,9 @@ static void ext_coset_fft(const e2 *coeffs, int log_len, u64 shift, e2 *out) {
 int zklc_oracle_plonky2_prove(const oparams *pr, const ogate *gates, const u64 *extra, const u64 *k_is, const u64 *constants,
                               const u64 *sigmas, const u64 *wires, const u64 *public_inputs, uint8_t *proof_out, u64 proof_cap,
                               u64 *proof_len, double *seconds, int nthreads, u64 *verifier_out) {
-    if (!pr || !gates || !k_is || !constants || !sigmas || !wires || !proof_out || !proof_len || pr->hasher != 0) return -1;
+    if (!pr || !gates || !k_is || !constants || !sigmas || !wires || !proof_out || !proof_len || pr->hasher > 1) return -1;
+    const int hs = (int)pr->hasher;
+    if (hs && !zklc_oracle_pbn_ready()) return -1;
 #ifdef _OPENMP
     omp_set_num_threads(nthreads > 0 ? nthreads : omp_get_num_procs());
 #endif
@@ -649,18 +681,21 @@ int zklc_oracle_plonky2_prove(const oparams *pr, const ogate *gates, const u64 *
         u64 *vals = malloc((u64)(nc + routed) * n * 8);
         memcpy(vals, constants, (u64)nc * n * 8);
         memcpy(vals + (u64)nc * n, sigmas, (u64)routed * n * 8);
-        batch_from_values(&cs, vals, nc + routed, db, rb, cap_h);
+        batch_from_values(&cs, hs, vals, nc + routed, db, rb, cap_h);
         free(vals);
     }
     const u32 cap_n = 1u << cs.tree.cap_height;
     u64 digest[4];
     {
-        u64 *parts = malloc((4 * cap_n + 5) * 8), pad[8] = {1, 0, 0, 0, 0, 0, 0, 1}, hp[4];
-        memcpy(parts, tree_cap(&cs.tree), 4 * cap_n * 8);
-        hash_no_pad(pad, 8, hp);
-        memcpy(parts + 4 * cap_n, hp, 32);
-        parts[4 * cap_n + 4] = (u64)db;
-        hash_no_pad(parts, 4 * cap_n + 5, digest);
+        /* hash_pad([]): 1, zeros, 1 -- pad10*1 to 8 elements under Poseidon-Goldilocks, to 9 under Poseidon-BN128 */
+        u64 *parts = malloc((5 * cap_n + 6) * 8), pad[9] = {1, 0, 0, 0, 0, 0, 0, 0, 0}, hp[4], np = 0;
+        const u64 pad_to = hs ? 9 : 8;
+        pad[pad_to - 1] = 1;
+        for (u32 k = 0; k < cap_n; k++) np += (u64)h_to_vec(hs, tree_cap(&cs.tree) + 4 * k, parts + np);
+        h_hash_no_pad(hs, pad, pad_to, hp);
+        np += (u64)h_to_vec(hs, hp, parts + np);
+        parts[np++] = (u64)db;
+        h_hash_no_pad(hs, parts, np, digest);
         free(parts);
     }
     if (verifier_out) {
@@ -674,12 +709,12 @@ int zklc_oracle_plonky2_prove(const oparams *pr, const ogate *gates, const u64 *
     hash_no_pad(public_inputs, pr->num_public_inputs, pih);
     chal_t ch;
     memset(&ch, 0, sizeof ch);
-    ch_observe_many(&ch, digest, 4);
+    ch_observe_hashes(&ch, hs, digest, 1);
     ch_observe_many(&ch, pih, 4);
 
     /* ---- wires */
-    batch_from_values(&wb, wires, nw, db, rb, cap_h);
-    ch_observe_many(&ch, tree_cap(&wb.tree), 4 * cap_n);
+    batch_from_values(&wb, hs, wires, nw, db, rb, cap_h);
+    ch_observe_hashes(&ch, hs, tree_cap(&wb.tree), cap_n);
     u64 betas[4], gammas[4], alphas[4];
     for (u32 c = 0; c < nch; c++) betas[c] = ch_challenge(&ch);
     for (u32 c = 0; c < nch; c++) gammas[c] = ch_challenge(&ch);
@@ -742,11 +777,11 @@ int zklc_oracle_plonky2_prove(const oparams *pr, const ogate *gates, const u64 *
             memcpy(vals + (u64)c * n, zpp + (u64)c * nchunks * n, n * 8);
             memcpy(vals + ((u64)nch + (u64)c * npp) * n, zpp + ((u64)c * nchunks + 1) * n, (u64)npp * n * 8);
         }
-        batch_from_values(&zb, vals, nch * nchunks, db, rb, cap_h);
+        batch_from_values(&zb, hs, vals, nch * nchunks, db, rb, cap_h);
         free(vals);
     }
     free(zpp);
-    ch_observe_many(&ch, tree_cap(&zb.tree), 4 * cap_n);
+    ch_observe_hashes(&ch, hs, tree_cap(&zb.tree), cap_n);
     for (u32 c = 0; c < nch; c++) alphas[c] = ch_challenge(&ch);
     t[2] = now_s() - t1;
     t1 = now_s();
@@ -841,10 +876,10 @@ int zklc_oracle_plonky2_prove(const oparams *pr, const ogate *gates, const u64 *
                 if (j < (u64)qdf * n) chunks[((u64)c * qdf) * n + j] = v;
             }
         }
-        batch_from_coeffs(&qb, chunks, nch * qdf, db, rb, cap_h);
+        batch_from_coeffs(&qb, hs, chunks, nch * qdf, db, rb, cap_h);
     }
     free(qv);
-    ch_observe_many(&ch, tree_cap(&qb.tree), 4 * cap_n);
+    ch_observe_hashes(&ch, hs, tree_cap(&qb.tree), cap_n);
     const e2 zeta = ch_ext(&ch);
     t[3] = now_s() - t1;
     t1 = now_s();
@@ -935,9 +970,9 @@ int zklc_oracle_plonky2_prove(const oparams *pr, const ogate *gates, const u64 *
             for (u64 i = 0; i < len; i++) rv[i] = values[bitrev(i, log_len)];
             fleaves[a] = rv;
             flog[a] = log_len - ab;
-            tree_build(&ftrees[a], (const u64 *)rv, 2 * arity, log_len - ab, cap_h);
+            tree_build(&ftrees[a], hs, (const u64 *)rv, 2 * arity, log_len - ab, cap_h);
             const u32 fcap = 1u << ftrees[a].cap_height;
-            ch_observe_many(&ch, tree_cap(&ftrees[a]), 4 * fcap);
+            ch_observe_hashes(&ch, hs, tree_cap(&ftrees[a]), fcap);
             for (u32 k = 0; k < 4 * fcap; k += 4) wr_hash(&W, tree_cap(&ftrees[a]) + k);
             const e2 beta = ch_ext(&ch);
             e2 *nc2 = malloc((len >> ab) * sizeof(e2));

@@ -44,8 +44,105 @@ def load():
         lib.zklc_oracle_bn254_msm_naive.argtypes = [u64p, u64p, ctypes.c_uint64, u64p]
         lib.zklc_oracle_bn254_msm.restype = ctypes.c_int
         lib.zklc_oracle_bn254_msm.argtypes = [u64p, u64p, ctypes.c_uint64, u64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        lib.zklc_oracle_pbn_init.restype = ctypes.c_int
+        lib.zklc_oracle_pbn_init.argtypes = [u64p, ctypes.c_uint32, u64p, ctypes.c_uint32, u64p, u64p]
+        lib.zklc_oracle_pbn_modulus.restype = None
+        lib.zklc_oracle_pbn_modulus.argtypes = [u64p]
+        lib.zklc_oracle_pbn_permute_many.restype = None
+        lib.zklc_oracle_pbn_permute_many.argtypes = [u64p, ctypes.c_uint64]
+        for f in (lib.zklc_oracle_pbn_hash_no_pad, lib.zklc_oracle_pbn_hash_or_noop):
+            f.restype = None
+            f.argtypes = [u64p, ctypes.c_uint64, ctypes.c_uint64, u64p]
+        lib.zklc_oracle_pbn_two_to_one.restype = None
+        lib.zklc_oracle_pbn_two_to_one.argtypes = [u64p, u64p, u64p]
+        lib.zklc_oracle_bn254_merkle_commit.restype = ctypes.c_int
+        lib.zklc_oracle_bn254_merkle_commit.argtypes = [u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, u64p,
+                                                        ctypes.c_int]
+        _pbn_init(lib)
         _lib = lib
     return _lib
+
+
+# ---- Poseidon-BN254 (oracle/c/poseidon_bn254_oracle.c) ----
+def fr_words(values):
+    """ints below 2^256 -> uint64 [len, 4], little-endian words"""
+    import numpy as np
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in values), dtype="<u8").reshape(-1, 4).copy()
+
+
+def fr_ints(words):
+    import numpy as np
+    a = np.ascontiguousarray(words, dtype="<u8").reshape(-1, 4)
+    return [int.from_bytes(row.tobytes(), "little") for row in a]
+
+
+def _pbn_init(lib):
+    """the round constants and matrices of tests/golden/poseidon_bn254.json (as oracle/poseidon_bn254.py holds them), handed to the
+    C once, before any of its OpenMP regions runs"""
+    from . import poseidon_bn254 as pbn
+    mod = fr_words([0])
+    lib.zklc_oracle_pbn_modulus(mod.ctypes.data)
+    assert fr_ints(mod) == [pbn.R]
+    c, s = fr_words(pbn.C), fr_words(pbn.S)
+    m, p = fr_words([x for row in pbn.M for x in row]), fr_words([x for row in pbn.PM for x in row])
+    rc = lib.zklc_oracle_pbn_init(c.ctypes.data, len(pbn.C), s.ctypes.data, len(pbn.S), m.ctypes.data, p.ctypes.data)
+    assert rc == 0, "zklc_oracle_pbn_init: rc %d" % rc
+
+
+def pbn_permute(state):
+    """four ints below 2^256 -> the permuted state (ints below r)"""
+    return pbn_permute_many([state])[0]
+
+
+def pbn_permute_many(states):
+    a = fr_words([x for st in states for x in st])
+    load().zklc_oracle_pbn_permute_many(a.ctypes.data, len(states))
+    out = fr_ints(a)
+    return [out[4 * i:4 * i + 4] for i in range(len(states))]
+
+
+def _pbn_hash(fn, gl_elems):
+    import numpy as np
+    a = np.array([int(x) for x in gl_elems] + [0], dtype=np.uint64)
+    out = np.zeros(4, dtype=np.uint64)
+    fn(a.ctypes.data, 1, len(gl_elems), out.ctypes.data)
+    return fr_ints(out)[0]
+
+
+def pbn_hash_no_pad(gl_elems):
+    return _pbn_hash(load().zklc_oracle_pbn_hash_no_pad, gl_elems)
+
+
+def pbn_hash_or_noop(gl_elems):
+    return _pbn_hash(load().zklc_oracle_pbn_hash_or_noop, gl_elems)
+
+
+def pbn_two_to_one(left, right):
+    import numpy as np
+    a = fr_words([left, right])
+    out = np.zeros(4, dtype=np.uint64)
+    load().zklc_oracle_pbn_two_to_one(a[0].ctypes.data, a[1].ctypes.data, out.ctypes.data)
+    return fr_ints(out)[0]
+
+
+def bn254_merkle_commit(mat, cap_height, nthreads=1):
+    """mat uint64 [width, n] (poly-major, canonical Goldilocks values) -> list of levels ([m, 4] arrays: one Fr in little-endian
+    words per digest), leaves first, cap last"""
+    import numpy as np
+    a = np.ascontiguousarray(mat, dtype=np.uint64)
+    width, n = a.shape
+    log_leaves = n.bit_length() - 1
+    assert n == 1 << log_leaves and 0 <= cap_height <= log_leaves
+    words = sum(4 << (log_leaves - l) for l in range(log_leaves - cap_height + 1))
+    tree = np.zeros(words, dtype=np.uint64)
+    rc = load().zklc_oracle_bn254_merkle_commit(a.ctypes.data, n, log_leaves, width, cap_height, tree.ctypes.data, nthreads)
+    assert rc > 0, rc
+    levels, off = [], 0
+    for l in range(log_leaves - cap_height + 1):
+        m = n >> l
+        levels.append(tree[off:off + 4 * m].reshape(m, 4))
+        off += 4 * m
+    return levels
 
 
 def ed25519_verify(pk, sig, msg):
@@ -153,10 +250,14 @@ class _OParams(ctypes.Structure):
 PLONKY2_PROVE_STAGES = ("preprocess", "wires_commit", "partial_products", "quotient", "openings", "fri", "proof", "threads")
 
 
-def plonky2_prove(data, wires, public_inputs, nthreads=0, verifier_data=False):
+HASH_GL, HASH_BN128 = 0, 1      # the values of zklc_amd.plonky2.serialization
+
+
+def plonky2_prove(data, wires, public_inputs, nthreads=0, verifier_data=False, hasher=HASH_GL):
     """One complete CPU proof with the C + OpenMP restatement.  `data`: a built circuit in the host builder's representation
     (read-only attribute access: degree_bits, config, gates with .code / .params, groups, selector_indices, k_is, constants,
-    sigmas, ..: the description the GPU library is given as well); wires uint64 [num_wires, n]; Poseidon-Goldilocks config.
+    sigmas, ..: the description the GPU library is given as well); wires uint64 [num_wires, n]; hasher: HASH_GL
+    (PoseidonGoldilocksConfig) or HASH_BN128 (PoseidonBN128GoldilocksConfig: the verifier data is decimal strings then).
     -> (proof bytes = ProofWithPublicInputs::to_bytes, {stage: seconds}) and, with verifier_data=True, the verifier-only data
     {"constants_sigmas_cap": [..], "circuit_digest": ..} in the JSON schema of the reference as a third item.  Raises ValueError for a circuit with gates outside
     the recursion set, AssertionError when the witness does not satisfy the copy constraints."""
@@ -170,7 +271,7 @@ def plonky2_prove(data, wires, public_inputs, nthreads=0, verifier_data=False):
     p.num_query_rounds = fri["num_query_rounds"]
     p.quotient_degree_factor, p.num_partial_products = data.quotient_degree_factor, data.num_partial_products
     p.num_gate_constraints, p.num_public_inputs = data.num_gate_constraints, data.num_public_inputs
-    p.hasher, p.num_gates, p.num_arities = 0, len(data.gates), len(data.fri_arity_bits)
+    p.hasher, p.num_gates, p.num_arities = int(hasher), len(data.gates), len(data.fri_arity_bits)
     for i, a in enumerate(data.fri_arity_bits):
         p.arity_bits[i] = a
     gates = (_OGate * len(data.gates))()
@@ -213,6 +314,9 @@ def plonky2_prove(data, wires, public_inputs, nthreads=0, verifier_data=False):
         raise ValueError("zklc_oracle_plonky2_prove: rc %d (unsupported gate / invalid argument / buffer)" % rc)
     res = (bytes(out[:ln.value]), dict(zip(PLONKY2_PROVE_STAGES, [float(x) for x in secs])))
     if verifier_data:
-        h = lambda k: {"elements": [int(x) for x in vd[4 * k:4 * k + 4]]}
+        if hasher == HASH_BN128:
+            h = lambda k: str(fr_ints(vd[4 * k:4 * k + 4])[0])
+        else:
+            h = lambda k: {"elements": [int(x) for x in vd[4 * k:4 * k + 4]]}
         res += ({"constants_sigmas_cap": [h(k) for k in range(cap_n)], "circuit_digest": h(cap_n)},)
     return res

@@ -5,11 +5,11 @@ proof-of-work bits, query rounds, routed wires that leave the permutation argume
 
 A case is a name, a circuit shape, a size and the entries it changes in a copy of the standard (135 wires) or wide (234 wires)
 configuration.  make(case) builds the circuit with a satisfying witness; reference(case) is the oracle's C prover's proof of it and
-its verifier data, computed once per case and process; batch(case) is that proof followed by its tampered copies."""
+its verifier data, computed once per case, hasher and process; batch(case) is that proof followed by its tampered copies."""
 import collections
 
 from oracle import cport
-from zklc_amd.plonky2 import CircuitBuilder, serialization as S, HASH_GL
+from zklc_amd.plonky2 import CircuitBuilder, serialization as S, HASH_GL, HASH_BN128
 from zklc_amd.plonky2 import synthetic as SY, gates as G, standard_recursion_config, wide_ecc_config
 from test_plonky2_verifier_host import tamper
 
@@ -43,9 +43,15 @@ PARAMETER_CASES = ([_case("arity-%d-%d" % af, "recursion", 7, arity=af) for af i
 CASES = SIZE_CASES + PARAMETER_CASES
 THREE_CHALLENGES = _case("challenges-3", "recursion", 6, nch=3)     # the host verifier takes it; the GPU prover holds two (P2_MAX_CH)
 BY_NAME = {c.name: c for c in CASES + [THREE_CHALLENGES]}
-BN128_CASES = [BY_NAME[k] for k in ("arity-2-2", "cap-0", "cap-7", "routed-73")]      # no C prover: the Python restatement
+BN128_CASES = [BY_NAME[k] for k in ("arity-2-2", "cap-0", "cap-7", "routed-73")]      # against the Python restatement
 LEAN_OFF_CASES = [BY_NAME[k] for k in ("arity-2-2", "cap-0", "routed-73", "combined-2^9")]
 assert len(CASES) == 45 and len(BY_NAME) == 46
+# Poseidon-BN128 against the C prover: every case of at most 2^11 rows, and two sizes of its own -- 2^12 rows (trees of 2^15 leaves:
+# the wrap's size, leaf digests from the one-lane kernel) and 2^13 rows (2^16 leaves: a one-lane tree level inside a proof)
+BN128_SIZE_CASES = [_case("recursion-2^%d" % d, "recursion", d) for d in (12, 13)]
+BN128_C_CASES = [c for c in CASES if c.degree_bits <= 11] + BN128_SIZE_CASES
+BY_NAME.update({c.name: c for c in BN128_SIZE_CASES})
+assert len(BN128_C_CASES) == 43 + 2 and len(BY_NAME) == 48
 
 
 def config(case):
@@ -97,13 +103,13 @@ def make(case):
     return _MADE[case.name]
 
 
-def reference(case):
+def reference(case, hasher=HASH_GL):
     """-> (proof bytes, verifier data) of the oracle's C prover"""
-    if case.name not in _REFERENCE:
+    if (case.name, hasher) not in _REFERENCE:
         data, wires, pis = make(case)
-        raw, _, vd = cport.plonky2_prove(data, wires, pis, nthreads=C_PROVER_THREADS, verifier_data=True)
-        _REFERENCE[case.name] = (raw, vd)
-    return _REFERENCE[case.name]
+        raw, _, vd = cport.plonky2_prove(data, wires, pis, nthreads=C_PROVER_THREADS, verifier_data=True, hasher=hasher)
+        _REFERENCE[case.name, hasher] = (raw, vd)
+    return _REFERENCE[case.name, hasher]
 
 
 def kinds(case):
@@ -121,10 +127,10 @@ def tampered(raw, common, vd, what, hasher=HASH_GL):
     return S.proof_to_bytes(tamper(S.proof_from_bytes(raw, common, hasher), common, vd, what), common, hasher)
 
 
-def batch(case):
+def batch(case, hasher=HASH_GL):
     """-> [the C prover's proof] + one tampered copy per kind of kinds(case), as bytes"""
-    if case.name not in _BATCH:
-        raw, vd = reference(case)
+    if (case.name, hasher) not in _BATCH:
+        raw, vd = reference(case, hasher)
         common = make(case)[0].common_data()
-        _BATCH[case.name] = [raw] + [tampered(raw, common, vd, k) for k in kinds(case)]
-    return _BATCH[case.name]
+        _BATCH[case.name, hasher] = [raw] + [tampered(raw, common, vd, k, hasher) for k in kinds(case)]
+    return _BATCH[case.name, hasher]

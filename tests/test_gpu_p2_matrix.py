@@ -1,6 +1,7 @@
 """The parameter matrix of tests/p2_matrix_cases.py on the GPU: for every case the GPU prover's bytes and verifier data equal the
 oracle's C prover's, and the GPU verifier gives the C prover's proof and its tampered copies the statuses of the host path
-(which tests/test_p2_matrix_host.py pins to the verifier restatement).  Four cases again under Poseidon-BN128 against the Python
+(which tests/test_p2_matrix_host.py pins to the verifier restatement).  The same under Poseidon-BN128 for every case of at most
+2^11 rows and for 2^12 and 2^13 rows (the wrap's size, and one above it), four cases again under Poseidon-BN128 against the Python
 prover restatement, the configuration with three challenges at the library's edges, and four cases with ZKLC_LEAN_ARITH=0."""
 import hashlib
 import os
@@ -27,11 +28,10 @@ def _verifier_half(v, batch):
             assert (st == PROOF_OK) == (i % len(batch) == 0), (i, got)
 
 
-@pytest.mark.parametrize("case", M.CASES, ids=lambda c: c.name)
-def test_prover_and_verifier_match_the_references(zctx, case):
+def _prover_and_verifier(zctx, case, hasher):
     data, wires, pis = M.make(case)
-    want, vd = M.reference(case)
-    prover = data.prover(zctx, HASH_GL)
+    want, vd = M.reference(case, hasher)
+    prover = data.prover(zctx, hasher)
     problems = []
     try:
         try:
@@ -46,10 +46,23 @@ def test_prover_and_verifier_match_the_references(zctx, case):
             problems.append("verifier data differs from the C prover's")
         # the verifier half takes its proofs from the C prover: it says something even where the prover half has failed
         with Verifier.from_prover(prover) as v:
-            _verifier_half(v, M.batch(case))
+            _verifier_half(v, M.batch(case, hasher))
     finally:
         prover.close()
     assert not problems, (case.name, data.fri_arity_bits, problems)
+
+
+@pytest.mark.parametrize("case", M.CASES, ids=lambda c: c.name)
+def test_prover_and_verifier_match_the_references(zctx, case):
+    _prover_and_verifier(zctx, case, HASH_GL)
+
+
+@pytest.mark.parametrize("case", M.BN128_C_CASES, ids=lambda c: c.name)
+def test_poseidon_bn128_prover_and_verifier_match_the_c_prover(zctx, case):
+    """PoseidonBN128GoldilocksConfig: the Merkle caps, and with them every challenge, differ from the Goldilocks configuration's, so
+    every stage upstream of the hash runs on other data here.  Proof bytes, a second prove_bytes, the verifier data, and the
+    verifier's statuses for the C prover's proof and its tampered copies."""
+    _prover_and_verifier(zctx, case, HASH_BN128)
 
 
 @pytest.mark.parametrize("case", M.BN128_CASES, ids=lambda c: c.name)

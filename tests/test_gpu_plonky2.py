@@ -128,16 +128,19 @@ def test_reference_sized_proofs_verify(zctx, shape, degree_bits, hasher):
         V.verify(json.loads(json.dumps(proof)), prover.verifier_data(), common)
 
 
-@pytest.mark.parametrize("shape,degree_bits", [("recursion", 12), ("ed25519", 13)])
-def test_gpu_proof_bytes_equal_the_c_prover_at_reference_sizes(zctx, shape, degree_bits):
+@pytest.mark.parametrize("shape,degree_bits,hasher", [("recursion", 12, HASH_GL), ("ed25519", 13, HASH_GL), ("recursion", 12, HASH_BN128)],
+                         ids=["recursion-12", "ed25519-13", "recursion-12-bn128"])
+def test_gpu_proof_bytes_equal_the_c_prover_at_reference_sizes(zctx, shape, degree_bits, hasher):
     """above ~2^8 rows the Python prover restatement is impractical and the tests relied on the verifier alone; the oracle's C
     prover (oracle/c/plonky2_prover_oracle.c, bytes equal to the Python restatement on small circuits: tests/test_oracle_cprover.py)
-    gives byte-level parity at the reference's sizes: 2^12 x 135 (recursion shape) and a 2^13 x 234 slice of the Ed25519 shape"""
+    gives byte-level parity at the reference's sizes: 2^12 x 135 (recursion shape) under both hashers -- under Poseidon-BN128 the
+    shape and size of the wrap, whose four trees of 2^15 leaves take the one-lane leaf kernel -- and a 2^13 x 234 slice of the
+    Ed25519 shape"""
     from oracle import cport
     data, wires, pis = _synthetic(shape, degree_bits, seed=5, npi=16)
-    prover = data.prover(zctx, HASH_GL)
+    prover = data.prover(zctx, hasher)
     got = prover.prove_bytes(wires, pis)
-    want, secs, vd = cport.plonky2_prove(data, wires, pis, verifier_data=True)
+    want, secs, vd = cport.plonky2_prove(data, wires, pis, verifier_data=True, hasher=hasher)
     assert prover.verifier_data() == vd
     assert got == want
     prover.close()
@@ -255,6 +258,11 @@ def test_prove_approvals_on_the_reference_small_fixture(zctx, approval_prover):
     wrap = RecursionProver(zctx, HASH_BN128)
     wrc, wproof = wrap.recursive_proof((rc.common, rc.verifier_only, proof))
     V.verify(json.loads(json.dumps(wproof)), wrc.verifier_only, wrc.common)
+    # the one proof that leaves the system, byte for byte: the C prover under Poseidon-BN128 on the very witness the GPU proved
+    wwant, _, wvd = cport.plonky2_prove(wrc.data, wrc.wire_buffer()[0].copy(), [int(x) for x in wproof["public_inputs"]],
+                                        verifier_data=True, hasher=HASH_BN128)
+    assert S.proof_to_bytes(wproof, wrc.common, HASH_BN128) == wwant, "GPU proof of the wrap circuit differs from the C prover's"
+    assert wrc.verifier_only == wvd
     golden = load_golden("plonky2_near_random_CGZP.json")["common_data"]
     assert wrc.common["gates"] == golden["gates"]      # the wrap circuit has the gate list of the reference's final proofs
     wrap.close()

@@ -6,9 +6,9 @@ import json
 import pytest
 
 import zklc_amd  # noqa: F401
-from zklc_amd.plonky2 import HASH_BN128, HASH_GL
+from zklc_amd.plonky2 import HASH_BN128, HASH_GL, serialization as S
 from zklc_amd.plonky2.recursion import RecursionProver
-from oracle import plonky2_verifier as V, poseidon_gl as pgl
+from oracle import cport, plonky2_verifier as V, poseidon_gl as pgl
 from test_recursion import _inner_circuit
 
 pytestmark = pytest.mark.gpu
@@ -40,6 +40,12 @@ def test_recursive_proof_valid_fold_wrap_and_invalid(zctx):
     wrap = RecursionProver(zctx, HASH_BN128)
     rcw, pw = wrap.recursive_proof((rc3.common, rc3.verifier_only, p3))
     V.verify(json.loads(json.dumps(pw)), rcw.verifier_only, rcw.common)
+    # the real wrap circuit, byte for byte: the oracle's C prover under Poseidon-BN128 on the very witness the GPU proved (the host
+    # interpreter left it in rcw.wire_buffer())
+    want, _, wvd = cport.plonky2_prove(rcw.data, rcw.wire_buffer()[0].copy(), [int(x) for x in pw["public_inputs"]],
+                                       verifier_data=True, hasher=HASH_BN128)
+    assert S.proof_to_bytes(pw, rcw.common, HASH_BN128) == want, "GPU proof of the wrap circuit differs from the C prover's"
+    assert rcw.verifier_only == wvd
     # recursion.rs:127-158: a modified public input of the inner proof -> no witness
     bad = json.loads(json.dumps(proof))
     bad["public_inputs"][-1] = 10000

@@ -88,3 +88,55 @@ def test_c_prover_refuses_unknown_gate_codes(inner):
     fake.gates = [g0] + list(data.gates[1:])
     with pytest.raises(ValueError):
         cport.plonky2_prove(fake, wires, pis)
+
+
+# ------------------------------------------------------------------------------------------------ PoseidonBN128GoldilocksConfig
+def _bn128_python(data, wires, pis):
+    common = data.common_data()
+    proof, vd = OP.prove(common, data.constants, data.sigmas, wires, pis, V.HasherBN128)
+    return S.proof_to_bytes(json.loads(json.dumps(proof)), common, S.HASH_BN128), json.loads(json.dumps(vd))
+
+
+def test_c_prover_bn128_bytes_equal_the_python_restatement(inner):
+    """the Merkle trees, the circuit digest and what the challenger observes of a digest under Poseidon-BN128
+    (oracle/c/poseidon_bn254_oracle.c); the public-input hash and the challenger stay Poseidon-Goldilocks.  Bytes and verifier
+    data (decimal strings) of the Python restatement, for 1 and 4 threads."""
+    data, wires, pis = inner[:3]
+    want, vd = _bn128_python(data, wires, pis)
+    got1, secs, vd_c = cport.plonky2_prove(data, wires, pis, nthreads=1, verifier_data=True, hasher=cport.HASH_BN128)
+    got4, _ = cport.plonky2_prove(data, wires, pis, nthreads=4, hasher=cport.HASH_BN128)
+    assert len(want) == S.proof_size(data.common_data(), S.HASH_BN128)
+    assert got1 == want and got4 == want
+    assert vd_c == vd and all(isinstance(h, str) for h in vd_c["constants_sigmas_cap"] + [vd_c["circuit_digest"]])
+    assert cport.HASH_GL == S.HASH_GL and cport.HASH_BN128 == S.HASH_BN128
+    # the Goldilocks configuration's proof of the same witness is another one
+    assert got1 != cport.plonky2_prove(data, wires, pis, nthreads=1)[0]
+
+
+def test_c_prover_bn128_every_gate_type_bytes_equal_the_python_restatement():
+    """the 2^6-row recursion-shaped circuit with every gate type of the recursion set"""
+    from zklc_amd.plonky2 import synthetic as SY, gates as G, standard_recursion_config
+    pgl.use_c_port()
+    cfg = standard_recursion_config()
+    mix = SY.recursion_shape_mix(cfg) + [(G.ExponentiationGate(20), 3)]
+    data, wires, pis = SY.synthetic_circuit(6, cfg, mix, num_public_inputs=11, seed=3)
+    want, vd = _bn128_python(data, wires, pis)
+    got, _, vd_c = cport.plonky2_prove(data, wires, pis, nthreads=2, verifier_data=True, hasher=cport.HASH_BN128)
+    assert got == want
+    assert vd_c == vd
+
+
+def test_c_prover_bn128_at_the_wrap_size_is_accepted_by_the_verifier():
+    """one 2^12 x 135 proof -- the wrap's shape: four trees of 2^15 leaves -- is accepted by the verifier restatement (all 28
+    query rounds), and one changed byte is not"""
+    from test_gpu_plonky2 import _synthetic
+    data, wires, pis = _synthetic("recursion", 12, seed=5, npi=16)
+    common = data.common_data()
+    got, secs, vd = cport.plonky2_prove(data, wires, pis, nthreads=8, verifier_data=True, hasher=cport.HASH_BN128)
+    assert wires.shape == (135, 1 << 12) and len(got) == S.proof_size(common, S.HASH_BN128)
+    V.verify(json.loads(json.dumps(S.proof_from_bytes(got, common, S.HASH_BN128))), vd, common)
+    print("complete C proof of a 2^12 x 135 circuit under Poseidon-BN128: %s" % {k: round(v, 3) for k, v in secs.items()})
+    t = bytearray(got)
+    t[40] ^= 1
+    with pytest.raises(AssertionError):
+        V.verify(json.loads(json.dumps(S.proof_from_bytes(bytes(t), common, S.HASH_BN128))), vd, common)
