@@ -465,26 +465,30 @@ __global__ void __launch_bounds__(256) poseidon_gl_permute_kernel(u64 *states, u
 
 // leaf i = (mat[p * stride + i * leaf_stride])_{p < width}; one lane per leaf.  Poly-major matrices (leaf_stride 1)
 // are coalesced across lanes for every p; leaf_stride = width, stride = 1 reads row-major leaves (FRI commit trees).
+// TAIL (here and in the two kernels below): the sponge / two_to_one compute only the words of the last MDS layer that are read
+// (poseidon_gl.cuh); false = every permutation whole, selected by ZKLC_PGL_TAIL=0 for A/B and byte-parity runs.
+template <bool TAIL>
 __global__ void __launch_bounds__(256)
 gl_hash_leaves_kernel(const u64 *__restrict__ mat, size_t stride, size_t leaf_stride, u32 width, u32 n_leaves,
                       u64 *__restrict__ digests) {
     u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_leaves) return;
     u64 h[4];
-    poseidon_gl_hash_or_noop(mat + (size_t)i * leaf_stride, stride, width, h);
+    poseidon_gl_hash_or_noop<TAIL>(mat + (size_t)i * leaf_stride, stride, width, h);
     ulonglong2 *o = reinterpret_cast<ulonglong2 *>(digests + (size_t)i * 4);
     o[0] = make_ulonglong2(h[0], h[1]);
     o[1] = make_ulonglong2(h[2], h[3]);
 }
 
 // parents[i] = two_to_one(children[2i], children[2i+1])
+template <bool TAIL>
 __global__ void __launch_bounds__(256) gl_merkle_level_kernel(const u64 *__restrict__ children, u64 *__restrict__ parents, u32 n_parents) {
     u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_parents) return;
     const ulonglong2 *c = reinterpret_cast<const ulonglong2 *>(children + (size_t)i * 8);
     ulonglong2 a = c[0], b = c[1], cc = c[2], dd = c[3];
     u64 l[4] = {a.x, a.y, b.x, b.y}, r[4] = {cc.x, cc.y, dd.x, dd.y}, h[4];
-    poseidon_gl_two_to_one(l, r, h);
+    poseidon_gl_two_to_one<TAIL>(l, r, h);
     ulonglong2 *o = reinterpret_cast<ulonglong2 *>(parents + (size_t)i * 4);
     o[0] = make_ulonglong2(h[0], h[1]);
     o[1] = make_ulonglong2(h[2], h[3]);
@@ -503,7 +507,7 @@ __global__ void __launch_bounds__(256) gl_merkle_level_kernel(const u64 *__restr
 struct gl_tail_levels {
     u64 *lvl[GL_MERKLE_TAIL_MAX_LEVELS + 1];   // lvl[0] = the children (read), lvl[1..nlev] = the parents' levels (written)
 };
-template <int T>
+template <int T, bool TAIL>
 __global__ void __launch_bounds__(T) gl_merkle_tail_kernel(gl_tail_levels L, u32 n_children, u32 nlev) {
     __shared__ ulonglong2 dig[T][2];
     const u32 tid = threadIdx.x;
@@ -523,7 +527,7 @@ __global__ void __launch_bounds__(T) gl_merkle_tail_kernel(gl_tail_levels L, u32
                 a = dig[2 * tid][0], b = dig[2 * tid][1], cc = dig[2 * tid + 1][0], dd = dig[2 * tid + 1][1];
             }
             u64 l[4] = {a.x, a.y, b.x, b.y}, r[4] = {cc.x, cc.y, dd.x, dd.y};
-            poseidon_gl_two_to_one(l, r, h);
+            poseidon_gl_two_to_one<TAIL>(l, r, h);
         }
         __syncthreads();                                    // every live lane has read its two children
         if (live) {
@@ -998,13 +1002,17 @@ int32_t zklc_gl_merkle_commit_strided(zklc_ctx *ctx, hipStream_t st, const uint6
     static const u32 tail_min_log = min_pin >= 4 && min_pin <= 14 ? (u32)min_pin : GL_MERKLE_TAIL_MIN_LOG;
     // ZKLC_MERKLE_FUSED=0 keeps one launch per level (A/B and the variant parity test)
     static const bool fused = !(getenv("ZKLC_MERKLE_FUSED") && getenv("ZKLC_MERKLE_FUSED")[0] == '0');
+    const bool tail = zklc_pgl_tail();   // ZKLC_PGL_TAIL=0: every permutation of the lane kernels whole (A/B)
     gl_merkle_plan plan;
     if (!gl_merkle_make_plan(log_leaves, cap_height, tail_t, mode, fused, tail_min_log, &plan)) return ZKLC_ERR_INVALID_ARG;
     if (plan.leaf_kind == GL_MERKLE_LEAVES_COOP)
         hipLaunchKernelGGL(gl_hash_leaves_coop_kernel, dim3(plan.leaf_grid), dim3(256), 0, st, d_mat, (size_t)stride, (size_t)leaf_stride,
                            width, n, d_tree);
+    else if (tail)
+        hipLaunchKernelGGL(gl_hash_leaves_kernel<true>, dim3(plan.leaf_grid), dim3(256), 0, st, d_mat, (size_t)stride, (size_t)leaf_stride,
+                           width, n, d_tree);
     else
-        hipLaunchKernelGGL(gl_hash_leaves_kernel, dim3(plan.leaf_grid), dim3(256), 0, st, d_mat, (size_t)stride, (size_t)leaf_stride,
+        hipLaunchKernelGGL(gl_hash_leaves_kernel<false>, dim3(plan.leaf_grid), dim3(256), 0, st, d_mat, (size_t)stride, (size_t)leaf_stride,
                            width, n, d_tree);
     ZKLC_HIP(ctx, hipGetLastError());
     for (u32 k = 0; k < plan.n; k++) {
@@ -1014,12 +1022,11 @@ int32_t zklc_gl_merkle_commit_strided(zklc_ctx *ctx, hipStream_t st, const uint6
         case GL_MERKLE_TAIL: {
             gl_tail_levels L;
             for (u32 j = 0; j <= GL_MERKLE_TAIL_MAX_LEVELS; j++) L.lvl[j] = j <= P.n_levels ? d_tree + P.off[j] : nullptr;
-            if (P.threads == 1024)
-                hipLaunchKernelGGL(gl_merkle_tail_kernel<1024>, dim3(P.grid), dim3(1024), 0, st, L, P.n_children, P.n_levels);
-            else if (P.threads == 512)
-                hipLaunchKernelGGL(gl_merkle_tail_kernel<512>, dim3(P.grid), dim3(512), 0, st, L, P.n_children, P.n_levels);
-            else
-                hipLaunchKernelGGL(gl_merkle_tail_kernel<256>, dim3(P.grid), dim3(256), 0, st, L, P.n_children, P.n_levels);
+            auto kern = P.threads == 1024  ? (tail ? gl_merkle_tail_kernel<1024, true> : gl_merkle_tail_kernel<1024, false>)
+                        : P.threads == 512 ? (tail ? gl_merkle_tail_kernel<512, true> : gl_merkle_tail_kernel<512, false>)
+                                           : (tail ? gl_merkle_tail_kernel<256, true> : gl_merkle_tail_kernel<256, false>);
+            hipLaunchKernelGGL(kern, dim3(P.grid), dim3(P.threads == 1024 || P.threads == 512 ? P.threads : 256), 0, st, L, P.n_children,
+                               P.n_levels);
             break;
         }
         case GL_MERKLE_SUBTREE_COOP: {
@@ -1033,8 +1040,8 @@ int32_t zklc_gl_merkle_commit_strided(zklc_ctx *ctx, hipStream_t st, const uint6
                                d_tree + P.off[1], parents);
             break;
         default:
-            hipLaunchKernelGGL(gl_merkle_level_kernel, dim3(P.grid), dim3(256), 0, st, (const u64 *)(d_tree + P.off[0]), d_tree + P.off[1],
-                               parents);
+            hipLaunchKernelGGL(tail ? gl_merkle_level_kernel<true> : gl_merkle_level_kernel<false>, dim3(P.grid), dim3(256), 0, st,
+                               (const u64 *)(d_tree + P.off[0]), d_tree + P.off[1], parents);
             break;
         }
         ZKLC_HIP(ctx, hipGetLastError());

@@ -1111,8 +1111,13 @@ struct p2_pow_args {
     u64 base;
     unsigned long long *found;
 };
+// TAIL: only s[7] is read, so the last full round computes rows 4..7 alone (poseidon_gl_permute_keep<4>), and a lane whose
+// candidate lies above a hit already recorded returns before hashing: it could never lower the minimum, so the witness is the
+// lowest hit of the launch whatever the timing, which decides only how many lanes skip.  false = as it was (ZKLC_PGL_TAIL=0).
+template <bool TAIL>
 __global__ void __launch_bounds__(P2_THREADS) p2_pow_kernel(p2_pow_args a) {
     u64 w = a.base + (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (TAIL && __hip_atomic_load(a.found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < w) return;
     u64 s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = a.state[i];
@@ -1122,7 +1127,8 @@ __global__ void __launch_bounds__(P2_THREADS) p2_pow_kernel(p2_pow_args a) {
 #pragma unroll
     for (int i = 0; i < 8; i++)
         if ((u32)i == a.n_in) s[i] = w;
-    poseidon_gl_permute(s);
+    if (TAIL) poseidon_gl_permute_keep<4>(s);
+    else poseidon_gl_permute(s);
     if ((s[7] >> (64 - a.pow_bits)) == 0) atomicMin(a.found, (unsigned long long)w);
 }
 
@@ -1986,7 +1992,8 @@ extern "C" int32_t zklc_plonky2_prove_dev(zklc_ctx *ctx, void *stream, zklc_plon
         for (u64 base = 0;; base += batch) {
             ZKLC_HIP(ctx, hipMemsetAsync(c->d_found, 0xFF, 8, st));
             a.base = base;
-            hipLaunchKernelGGL(p2_pow_kernel, dim3((unsigned)(batch / P2_THREADS)), dim3(P2_THREADS), 0, st, a);
+            hipLaunchKernelGGL(zklc_pgl_tail() ? p2_pow_kernel<true> : p2_pow_kernel<false>, dim3((unsigned)(batch / P2_THREADS)),
+                               dim3(P2_THREADS), 0, st, a);
             ZKLC_HIP(ctx, hipGetLastError());
             ZKLC_HIP(ctx, zklc_readback_async(h_found, c->d_found, 8, st));
             ZKLC_HIP(ctx, zklc_stream_wait(st));

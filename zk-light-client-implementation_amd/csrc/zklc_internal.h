@@ -134,6 +134,13 @@ inline bool zklc_lean_arith() {
     static const bool on = !(getenv("ZKLC_LEAN_ARITH") && getenv("ZKLC_LEAN_ARITH")[0] == '0');
     return on;
 }
+// ZKLC_PGL_TAIL=0 restores, in the leaf, level and tail kernels of a Goldilocks Merkle tree and in the proof-of-work kernel, the forms
+// that run every Poseidon permutation whole (A/B and byte-parity runs); by default the last full round computes only the rows of its
+// MDS layer that are read afterwards (poseidon_gl.cuh).  Digests, witnesses and proof bytes are the same under both settings.
+inline bool zklc_pgl_tail() {
+    static const bool on = !(getenv("ZKLC_PGL_TAIL") && getenv("ZKLC_PGL_TAIL")[0] == '0');
+    return on;
+}
 inline hipError_t zklc_readback_async(void *dst, const void *src, size_t bytes, hipStream_t st) {
     if (zklc_settled_copies()) {
         hipError_t e = zklc_stream_wait(st);
