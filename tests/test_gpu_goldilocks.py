@@ -87,6 +87,16 @@ def test_big_tile_sizes_match_oracle(zctx, log_n, rate_bits):
         assert np.array_equal(zctx.gl_lde(c, rate_bits, 7), cport.gl_lde(c, rate_bits, 7, nthreads=8))
 
 
+def test_three_pass_size_matches_oracle(zctx):
+    """2^23 is the smallest size whose default plan has three passes (csrc/gl_ntt_plan.h; 2^23 and 2^24 are accepted by
+    zklc_plonky2_circuit_create): one polynomial forward to bit-reversed order against the C oracle, and the inverse brings it back"""
+    rng = np.random.default_rng(523)
+    a = rand_gl(rng, (1, 1 << 23))
+    f = zctx.gl_ntt(a, flags=OUT_BR)
+    assert np.array_equal(f[:, bitrev_fast(23)], cport.gl_ntt(a, nthreads=8))
+    assert np.array_equal(zctx.gl_ntt(f, flags=INV | IN_BR), a)
+
+
 def bitrev_fast(bits):
     idx = np.arange(1 << bits, dtype=np.uint64)
     out = np.zeros_like(idx)

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Code size and register count of the Poseidon-Goldilocks hash kernels, read from the gfx950 code objects in build/*.o: the symbol
-size of each kernel's function (the 64 KB instruction cache is the condition the leaf kernel's single looped copy of the full-round
-statement exists for) and the VGPR / scratch figures of the kernel descriptor's metadata (above 128 VGPRs a SIMD holds three waves
-instead of four).  Needs no GPU.
+"""Code size and register count of the Poseidon-Goldilocks hash kernels and of the Goldilocks NTT pass kernels, read from the gfx950
+code objects in build/*.o.  Needs no GPU.
+
+The symbol size of each kernel's function: the 64 KB instruction cache is the condition the leaf kernel's single looped copy of the
+full-round statement exists for.  The VGPR / scratch figures of the kernel descriptor's metadata: above 128 VGPRs a SIMD holds three
+waves instead of four, and the forward-order shift-twiddle NTT pass sits at exactly 128.
 
     python tools/kernel_code_size.py [build-dir]      # one line per kernel: code bytes, VGPRs, scratch bytes, mangled name
 """
@@ -15,7 +17,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "zk-light-client-implementation_amd", "build")
 LLVM = "/opt/rocm/lib/llvm/bin"
-KERNELS = {"goldilocks_hip.o": ("gl_hash_leaves_kernel", "gl_merkle_level_kernel", "gl_merkle_tail_kernel"),
+KERNELS = {"goldilocks_hip.o": ("gl_hash_leaves_kernel", "gl_merkle_level_kernel", "gl_merkle_tail_kernel", "gl_ntt_pass_"),
            "plonky2_prover_hip.o": ("p2_pow_kernel",)}
 
 

@@ -13,16 +13,12 @@
 #include <string.h>
 #include "poseidon_gl.cuh"
 #include "gl_merkle_plan.h"
+#include "gl_ntt_plan.h"
 #include "goldilocks_ntt_group.cuh"
 #include <mutex>
 #include "zklc_internal.h"
 
-#define NTT_THREADS 256
-#define NTT_TILE_LOG_MAX 12
 #define NTT_TILE_MAX (1 << NTT_TILE_LOG_MAX)
-// the radix-8 pass kernel takes its tile as dynamic LDS: 2^12 elements (36 KB with padding, 256 threads) or 2^13 (72 KB, 512 threads)
-#define NTT_TILE_LOG_BIG 13
-#define NTT_THREADS_MAX 512
 
 // ---------------------------------------------------------------- tables
 __global__ void gl_pow_table_kernel(u64 *out, u64 base, u64 n, u64 exp_stride) {
@@ -55,18 +51,10 @@ __global__ void gl_staged_twiddle_kernel(u64 *out, u64 w, u32 logn) {
 // twiddle w^((i mod h) << s), h = 2^(logn-1-s), from the table tw[i] = w^i, i < 2^(logn-1).
 //   DIF (forward order of stages): natural-order input -> bit-reversed output
 //   DIT (reverse order of stages): bit-reversed input  -> natural-order output
-struct ntt_pass {
-    int logn, s0, k, c, d;
-    int log_in;        // input indices >= 2^log_in read as zero (LDE zero padding); = logn otherwise
-    int scale_shift;   // log2 of the low table size of the two-level load scale (0 = no load scale)
-    u64 out_scale;     // multiplied into every stored value when != 1 (1/n of the inverse transform)
-    // shift-twiddle kernel (gl_ntt_pass_g4_kernel): the k stages in ng groups of gsz[i] <= 4 stages (top stage first); goff[i] =
-    // offset of the group's block in the table of per-element twiddles (gl_get_group_twiddles)
-    int ng, gsz[4];
-    u64 goff[4];
-    int zskip_ok;      // the zero-aware first group of an 8x LDE may be used (off: ZKLC_NTT_ZSKIP=0)
-};
-
+// Which stages a pass takes, its groups, their table blocks and the launch shape (struct ntt_pass, gl_ntt_make_plan), and the index
+// maps the kernels below use (tile -> transform index, group -> tile element and table entry) are in gl_ntt_plan.h, plain C++:
+// tests/ntt_plan_host checks the plan's conditions at every accepted size (logn 1..24, both tiles, the three-pass plans included)
+// and runs it on the CPU -- the same index maps, gl_ntt_group_regs and table layout -- against a plain radix-2 transform.
 template <bool DIT>
 __global__ void __launch_bounds__(NTT_THREADS)
 gl_ntt_pass_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t in_stride, size_t out_stride, ntt_pass p,
@@ -77,23 +65,13 @@ gl_ntt_pass_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t in_
     const int lowbits = p.logn - p.s0 - p.k;
     const u32 tid = threadIdx.x;
     // tile coordinates
-    const u64 t_id = blockIdx.x;
-    const u64 tileL = t_id & ((1ULL << (lowbits - p.c)) - 1);
-    const u64 tileH = t_id >> (lowbits - p.c);
+    u64 tileL, tileH;
+    gl_ntt_tile_split(p, lowbits, blockIdx.x, &tileL, &tileH);
     const u64 *src = in + (size_t)blockIdx.y * in_stride;
     u64 *dst = out + (size_t)blockIdx.y * out_stride;
 
-    auto global_index = [&](u32 e) -> u64 {
-        u64 lowc = e & ((1u << p.c) - 1);
-        u64 mid = (e >> p.c) & ((1u << p.k) - 1);
-        u64 hid = e >> (p.c + p.k);
-        u64 L = (tileL << p.c) | lowc;
-        u64 H = (tileH << p.d) | hid;
-        return (H << (lowbits + p.k)) | (mid << lowbits) | L;
-    };
-
     for (u32 e = tid; e < (u32)tile_n; e += NTT_THREADS) {
-        u64 g = global_index(e);
+        u64 g = gl_ntt_global_index(p, lowbits, tileL, tileH, e);
         u64 v = 0;
         if (g < (1ULL << p.log_in)) {
             v = src[g];
@@ -130,7 +108,7 @@ gl_ntt_pass_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t in_
     for (u32 e = tid; e < (u32)tile_n; e += NTT_THREADS) {
         u64 v = tile[e];
         if (p.out_scale != 1) v = gl_mul(v, p.out_scale);
-        dst[global_index(e)] = v;
+        dst[gl_ntt_global_index(p, lowbits, tileL, tileH, e)] = v;
     }
 }
 
@@ -183,23 +161,13 @@ gl_ntt_pass_r8_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
     const int tile_n = 1 << tile_log;
     const int lowbits = p.logn - p.s0 - p.k;
     const u32 tid = threadIdx.x;
-    const u64 t_id = blockIdx.x;
-    const u64 tileL = t_id & ((1ULL << (lowbits - p.c)) - 1);
-    const u64 tileH = t_id >> (lowbits - p.c);
+    u64 tileL, tileH;
+    gl_ntt_tile_split(p, lowbits, blockIdx.x, &tileL, &tileH);
     const u64 *src = in + (size_t)blockIdx.y * in_stride;
     u64 *dst = out + (size_t)blockIdx.y * out_stride;
 
-    auto global_index = [&](u32 e) -> u64 {
-        u64 lowc = e & ((1u << p.c) - 1);
-        u64 mid = (e >> p.c) & ((1u << p.k) - 1);
-        u64 hid = e >> (p.c + p.k);
-        u64 L = (tileL << p.c) | lowc;
-        u64 H = (tileH << p.d) | hid;
-        return (H << (lowbits + p.k)) | (mid << lowbits) | L;
-    };
-
     for (u32 e = tid; e < (u32)tile_n; e += n_threads) {
-        u64 g = global_index(e);
+        u64 g = gl_ntt_global_index(p, lowbits, tileL, tileH, e);
         u64 v = 0;
         if (g < (1ULL << p.log_in)) {
             v = src[g];
@@ -219,10 +187,8 @@ gl_ntt_pass_r8_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
         const int hi_shift = mg + lowbits;
         const u32 n_groups = (u32)tile_n >> g;
         for (u32 gi = tid; gi < n_groups; gi += n_threads) {
-            u32 base = ((gi >> pb_low) << (pb_low + g)) | (gi & ((1u << pb_low) - 1));
-            u64 lowc = base & ((1u << p.c) - 1);
-            u64 mid_low = (base >> p.c) & ((1u << mg) - 1);
-            u64 J = (mid_low << lowbits) | ((tileL << p.c) | lowc);
+            u32 base = gl_ntt_group_base(gi, pb_low, g);
+            u64 J = gl_ntt_group_J(p, lowbits, tileL, base, mg);
             if (g == 3)
                 gl_ntt_group<3, DIT>(tile, tw, 1ULL << p.logn, base, pb_low, J, sh, hi_shift);
             else if (g == 2)
@@ -237,7 +203,7 @@ gl_ntt_pass_r8_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
     for (u32 e = tid; e < (u32)tile_n; e += n_threads) {
         u64 v = tile[NTT_TI(e)];
         if (p.out_scale != 1) v = gl_mul(v, p.out_scale);
-        dst[global_index(e)] = v;
+        dst[gl_ntt_global_index(p, lowbits, tileL, tileH, e)] = v;
     }
 }
 
@@ -281,29 +247,19 @@ gl_ntt_pass_g4_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
     const int tile_n = 1 << tile_log;
     const int lowbits = p.logn - p.s0 - p.k;
     const u32 tid = threadIdx.x;
-    const u64 t_id = blockIdx.x;
-    const u64 tileL = t_id & ((1ULL << (lowbits - p.c)) - 1);
-    const u64 tileH = t_id >> (lowbits - p.c);
+    u64 tileL, tileH;
+    gl_ntt_tile_split(p, lowbits, blockIdx.x, &tileL, &tileH);
     const u64 *src = in + (size_t)blockIdx.y * in_stride;
     u64 *dst = out + (size_t)blockIdx.y * out_stride;
-
-    auto global_index = [&](u32 e) -> u64 {
-        u64 lowc = e & ((1u << p.c) - 1);
-        u64 mid = (e >> p.c) & ((1u << p.k) - 1);
-        u64 hid = e >> (p.c + p.k);
-        u64 L = (tileL << p.c) | lowc;
-        u64 H = (tileH << p.d) | hid;
-        return (H << (lowbits + p.k)) | (mid << lowbits) | L;
-    };
 
     // tile load, eight elements of a lane at a time with all eight global loads in flight (one load -> wait -> LDS write per
     // iteration exposed the HBM latency sixteen times per tile: 39 % of the wave cycles were SQ_WAIT_ANY).  The zero padding of an
     // LDE (7 of 8 elements of its first pass) issues no load.
-    // Index arithmetic (round 4): element e = tid | hi with hi a multiple of the (power-of-two) workgroup size; global_index scatters
+    // Index arithmetic (round 4): element e = tid | hi with hi a multiple of the (power-of-two) workgroup size; gl_ntt_global_index scatters
     // disjoint bit fields of e to disjoint bit fields of the global index and NTT_TJ is additive over them, so the lane's part is
     // computed ONCE (g_tid, lds_tid) and the `hi` part of every element is wave-uniform scalar work: one OR per element instead of
     // re-deriving three bit fields (~12 % of the pass's VALU instructions went into these index computations).
-    const u64 g_tid = global_index(tid);
+    const u64 g_tid = gl_ntt_global_index(p, lowbits, tileL, tileH, tid);
     const u32 lds_tid = NTT_TJ(tid);
     const bool lane_in = tid < (u32)tile_n;               // tiles smaller than the workgroup (small transforms)
     // Zero padding of an 8x LDE (round 6): the first pass of a DIF transform sees its window bits on top, so the padded positions
@@ -323,7 +279,7 @@ gl_ntt_pass_g4_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
 #pragma unroll
             for (int q = 0; q < LD; q++) {
                 const u32 hi = hi0 + q * n_threads;                      // wave-uniform
-                g[q] = hi < load_n ? (g_tid | global_index(hi)) : g_tid;
+                g[q] = hi < load_n ? (g_tid | gl_ntt_global_index(p, lowbits, tileL, tileH, hi)) : g_tid;
                 v[q] = 0;
                 if (lane_ld && g[q] < lim) v[q] = src[g[q]];          // predicated, still all in flight: nothing below waits before the batch is issued
             }
@@ -360,7 +316,7 @@ gl_ntt_pass_g4_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
         if constexpr (LEAN) {
             if (nj == 1) {       // the unit-twiddle group (J = 0 only): no table loads, no multiplications; a loop of its own
                 for (u32 gi = tid; gi < n_groups; gi += n_threads) {
-                    const u32 base = ((gi >> pb_low) << (pb_low + g)) | (gi & ((1u << pb_low) - 1));
+                    const u32 base = gl_ntt_group_base(gi, pb_low, g);
                     if (!DIT && zskip && gi_ == 0) {   // a one-group LDE (2^0..2^1 -> 2^3..2^4): zero-aware and unit at once
                         if (g == 4)
                             gl_ntt_group_lds<4, DIT, INV, DIT ? 0 : 3, true, true>(tile, gtab, nj, base, pb_low);
@@ -380,10 +336,8 @@ gl_ntt_pass_g4_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
             }
         }
         for (u32 gi = tid; gi < n_groups; gi += n_threads) {
-            u32 base = ((gi >> pb_low) << (pb_low + g)) | (gi & ((1u << pb_low) - 1));
-            u64 lowc = base & ((1u << p.c) - 1);
-            u64 mid_low = (base >> p.c) & ((1u << mg) - 1);
-            u64 J = (mid_low << lowbits) | ((tileL << p.c) | lowc);
+            u32 base = gl_ntt_group_base(gi, pb_low, g);
+            u64 J = gl_ntt_group_J(p, lowbits, tileL, base, mg);
             if constexpr (!DIT) {
                 if (zskip && gi_ == 0) {               // wave-uniform
                     if (g == 4)
@@ -420,19 +374,19 @@ gl_ntt_pass_g4_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, size_t 
             for (int q = 0; q < LD; q++) {
                 const u32 hi = hi0 + q * n_threads;
                 if (hi >= (u32)tile_n || !lane_in) continue;
-                dst[g_tid | global_index(hi)] = p.out_scale != 1 ? gl_mul(v[q], p.out_scale) : v[q];
+                dst[g_tid | gl_ntt_global_index(p, lowbits, tileL, tileH, hi)] = p.out_scale != 1 ? gl_mul(v[q], p.out_scale) : v[q];
             }
         }
     }
 }
 
-// block of one group in the table of per-element twiddles: out[(m - 1) * nj + J] = w^((bitrev_g(m) * J) << s_first), 1 <= m < 2^g
+// block of one group in the table of per-element twiddles (layout: gl_ntt_plan.h), one lane per entry (m, J), 1 <= m < 2^g
 __global__ void gl_group_twiddle_kernel(u64 *out, u64 w, u32 g, u32 s_first, u64 nj) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ((1ULL << g) - 1) * nj) return;
     u32 m = 1 + (u32)(i / nj);
     u64 J = i % nj;
-    out[i] = gl_pow(w, ((u64)gl_bitrev_small(m, (int)g) * J) << s_first);
+    out[gl_ntt_group_table_index(m, nj, J)] = gl_pow(w, gl_ntt_group_table_exponent(m, (int)g, J, (int)s_first));
 }
 
 // bit reversal of every polynomial of a batch
@@ -689,52 +643,63 @@ static u64 host_gl_pow(u64 a, u64 e) {
 }
 
 void zklc_gl_fini(zklc_ctx *ctx) {
-    for (int i = 0; i <= ZKLC_GL_MAX_LOG; i++) {
-        if (ctx->gl_tw_fwd[i]) (void)hipFree(ctx->gl_tw_fwd[i]);
-        if (ctx->gl_tw_inv[i]) (void)hipFree(ctx->gl_tw_inv[i]);
-        if (ctx->gl_tws_fwd[i]) (void)hipFree(ctx->gl_tws_fwd[i]);
-        if (ctx->gl_tws_inv[i]) (void)hipFree(ctx->gl_tws_inv[i]);
-        if (ctx->gl_twg_fwd[i]) (void)hipFree(ctx->gl_twg_fwd[i]);
-        if (ctx->gl_twg_inv[i]) (void)hipFree(ctx->gl_twg_inv[i]);
-        ctx->gl_tw_fwd[i] = ctx->gl_tw_inv[i] = ctx->gl_tws_fwd[i] = ctx->gl_tws_inv[i] = nullptr;
-        ctx->gl_twg_fwd[i] = ctx->gl_twg_inv[i] = nullptr;
-    }
+    for (auto &kind : ctx->gl_ntt_tab)
+        for (auto &dir : kind)
+            for (void *&tab : dir) {
+                if (tab) (void)hipFree(tab);
+                tab = nullptr;
+            }
     if (ctx->gl_scale_hi) (void)hipFree(ctx->gl_scale_hi);
     if (ctx->gl_scale_lo) (void)hipFree(ctx->gl_scale_lo);
     ctx->gl_scale_hi = ctx->gl_scale_lo = nullptr;
 }
 
-// twiddle tables w^i (i < n/2) for the forward and inverse transforms of size 2^logn
-static int32_t gl_get_twiddles(zklc_ctx *ctx, hipStream_t st, int logn, bool inverse, const u64 **out) {
-    void **slot = inverse ? &ctx->gl_tw_inv[logn] : &ctx->gl_tw_fwd[logn];
+// The three pass kernels; each reads a twiddle table of its own kind (ctx->gl_ntt_tab[family]):
+enum gl_ntt_family {
+    GL_NTT_RADIX2 = 0,   // gl_ntt_pass_kernel, flat table w^i, i < n/2                                      (ZKLC_NTT_RADIX2, A/B)
+    GL_NTT_R8 = 1,       // gl_ntt_pass_r8_kernel, staged table (gl_staged_twiddle_kernel), n entries         (ZKLC_NTT_R8, A/B)
+    GL_NTT_G4 = 2,       // gl_ntt_pass_g4_kernel, group table (gl_group_twiddle_kernel), plan.table_elems    (the product path)
+};
+typedef void (*gl_ntt_pass_fn)(const u64 *, u64 *, size_t, size_t, ntt_pass, const u64 *, const u64 *, const u64 *);
+// every instantiation of the pass kernels, [family][dit][inverse][lean]; only the shift-twiddle kernel has forms per direction and
+// arithmetic (ZKLC_LEAN_ARITH): the radix-2 and radix-8 rows repeat their two instantiations over the other two indices
+static gl_ntt_pass_fn gl_ntt_pass_kernel_of(int family, bool dit, bool inverse, bool lean) {
+#define GL_NTT_ALL_FORMS(fn) {{fn, fn}, {fn, fn}}
+#define GL_NTT_G4_FORMS(dit) \
+    {{gl_ntt_pass_g4_kernel<dit, false, false>, gl_ntt_pass_g4_kernel<dit, false, true>}, \
+     {gl_ntt_pass_g4_kernel<dit, true, false>, gl_ntt_pass_g4_kernel<dit, true, true>}}
+    static const gl_ntt_pass_fn table[3][2][2][2] = {
+        {GL_NTT_ALL_FORMS(gl_ntt_pass_kernel<false>), GL_NTT_ALL_FORMS(gl_ntt_pass_kernel<true>)},
+        {GL_NTT_ALL_FORMS(gl_ntt_pass_r8_kernel<false>), GL_NTT_ALL_FORMS(gl_ntt_pass_r8_kernel<true>)},
+        {GL_NTT_G4_FORMS(false), GL_NTT_G4_FORMS(true)}};
+#undef GL_NTT_ALL_FORMS
+#undef GL_NTT_G4_FORMS
+    return table[family][dit][inverse][lean];
+}
+
+// The twiddle table of one (family, logn, direction), resident per context and built on first use: `fill(table, w)` enqueues the
+// kernels that write its `elems` entries from the 2^logn-th root of unity w.  The build is serialised and COMPLETE before the
+// pointer is published (another host thread or stream of the same context must never see a half-built table): one wait per table.
+static std::mutex gl_ntt_tab_mutex;
+template <class Fill>
+static int32_t gl_ntt_get_table(zklc_ctx *ctx, hipStream_t st, int family, int logn, bool inverse, u64 elems, Fill fill,
+                                const u64 **out) {
+    std::lock_guard<std::mutex> lock(gl_ntt_tab_mutex);
+    void **slot = &ctx->gl_ntt_tab[family][inverse][logn];
     if (!*slot) {
-        u64 n_half = logn ? (1ULL << (logn - 1)) : 1;
-        ZKLC_HIP(ctx, hipMalloc(slot, n_half * 8));
+        void *fresh = nullptr;
+        ZKLC_HIP(ctx, hipMalloc(&fresh, elems * 8));
         u64 w = host_gl_pow(GL_POWER_OF_TWO_GENERATOR, 1ULL << (32 - logn));
         if (inverse) w = host_gl_pow(w, GL_P - 2);
-        hipLaunchKernelGGL(gl_pow_table_kernel, dim3((unsigned)((n_half + 255) / 256)), dim3(256), 0, st, (u64 *)*slot, w, n_half,
-                           (u64)1);
+        fill((u64 *)fresh, w);
         ZKLC_HIP(ctx, hipGetLastError());
+        ZKLC_HIP(ctx, zklc_stream_wait(st));
+        *slot = fresh;
     }
     *out = (const u64 *)*slot;
     return ZKLC_OK;
 }
 
-static int32_t gl_get_staged_twiddles(zklc_ctx *ctx, hipStream_t st, int logn, bool inverse, const u64 **out) {
-    void **slot = inverse ? &ctx->gl_tws_inv[logn] : &ctx->gl_tws_fwd[logn];
-    if (!*slot) {
-        u64 n = 1ULL << logn;
-        ZKLC_HIP(ctx, hipMalloc(slot, n * 8));
-        u64 w = host_gl_pow(GL_POWER_OF_TWO_GENERATOR, 1ULL << (32 - logn));
-        if (inverse) w = host_gl_pow(w, GL_P - 2);
-        hipLaunchKernelGGL(gl_staged_twiddle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (u64 *)*slot, w, (u32)logn);
-        ZKLC_HIP(ctx, hipGetLastError());
-    }
-    *out = (const u64 *)*slot;
-    return ZKLC_OK;
-}
-
-#define GL_SCALE_LO_LOG 10
 // two-level table of shift^j: hi[j >> 10] * lo[j & 1023]
 static int32_t gl_get_scale(zklc_ctx *ctx, hipStream_t st, u64 shift, int logn) {
     int hi_n = logn > GL_SCALE_LO_LOG ? (1 << (logn - GL_SCALE_LO_LOG)) : 1;
@@ -763,151 +728,67 @@ static int32_t gl_ntt_run(zklc_ctx *ctx, hipStream_t st, const u64 *in, size_t i
                 ZKLC_HIP(ctx, hipMemcpyAsync(out + b * out_stride, in + b * in_stride, 8, hipMemcpyDeviceToDevice, st));
         return ZKLC_OK;
     }
-    static const bool radix2 = getenv("ZKLC_NTT_RADIX2") != nullptr;   // A/B switch: the original one-stage-per-barrier loop
-    static const bool r8 = getenv("ZKLC_NTT_R8") != nullptr;           // A/B switch: radix-8 groups with a table twiddle per butterfly
+    // the A/B switches
+    static const bool radix2 = getenv("ZKLC_NTT_RADIX2") != nullptr;   // the original one-stage-per-barrier loop
+    static const bool r8 = getenv("ZKLC_NTT_R8") != nullptr;           // radix-8 groups with a table twiddle per butterfly
+    static const int tile_pin = getenv("ZKLC_NTT_TILE") ? atoi(getenv("ZKLC_NTT_TILE")) : 0;   // 12 | 13 pins the tile
+    static const bool zskip_on = !(getenv("ZKLC_NTT_ZSKIP") && getenv("ZKLC_NTT_ZSKIP")[0] == '0');
+    const bool lean = zklc_lean_arith();                                // ZKLC_LEAN_ARITH
+    const int family = radix2 ? GL_NTT_RADIX2 : r8 ? GL_NTT_R8 : GL_NTT_G4;
     const bool lds_ok = zklc_once_per_device([] {     // 72 KB of dynamic LDS is above the default 64 KB cap
         const int bytes = ((1 << NTT_TILE_LOG_BIG) + (1 << NTT_TILE_LOG_BIG) / 8) * (int)sizeof(u64);
-        const void *fns[10] = {(const void *)gl_ntt_pass_r8_kernel<true>,               (const void *)gl_ntt_pass_r8_kernel<false>,
-                               (const void *)gl_ntt_pass_g4_kernel<true, true, true>,   (const void *)gl_ntt_pass_g4_kernel<true, false, true>,
-                               (const void *)gl_ntt_pass_g4_kernel<false, true, true>,  (const void *)gl_ntt_pass_g4_kernel<false, false, true>,
-                               (const void *)gl_ntt_pass_g4_kernel<true, true, false>,  (const void *)gl_ntt_pass_g4_kernel<true, false, false>,
-                               (const void *)gl_ntt_pass_g4_kernel<false, true, false>, (const void *)gl_ntt_pass_g4_kernel<false, false, false>};
-        for (const void *f : fns) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return e;
-        }
+        for (int fam : {GL_NTT_R8, GL_NTT_G4})      // the radix-2 kernel's tile is static; only dit (bit 0) tells the r8 forms apart
+            for (int form = 0; form < (fam == GL_NTT_G4 ? 8 : 2); form++) {
+                hipError_t e = hipFuncSetAttribute((const void *)gl_ntt_pass_kernel_of(fam, form & 1, form & 2, form & 4),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+                if (e != hipSuccess) return e;
+            }
         return hipSuccess;
     }) == hipSuccess;
     if (!lds_ok) return ZKLC_ERR_HIP;
-    const bool g4 = !radix2 && !r8;
-    const u64 *tw = nullptr;
+
+    gl_ntt_plan plan;
+    const u64 n_inv = inverse ? host_gl_pow(1ULL << logn, GL_P - 2) : 1;
+    if (!gl_ntt_make_plan(logn, log_in, radix2, tile_pin, zskip_on, load_shift != 0, n_inv, &plan)) return ZKLC_ERR_INVALID_ARG;
+
     int32_t rc = ZKLC_OK;
-    if (!g4) rc = radix2 ? gl_get_twiddles(ctx, st, logn, inverse, &tw) : gl_get_staged_twiddles(ctx, st, logn, inverse, &tw);
-    if (rc) return rc;
     if (load_shift) {
         if ((rc = gl_get_scale(ctx, st, load_shift, log_in))) return rc;
     }
-    // plan: strided windows from the top (each leaves >= 4 low bits in the tile: 128-byte runs), then one contiguous window.
-    // Tile of 2^12 elements, or 2^13 where that saves a whole pass over the data (e.g. 2^21: two passes instead of three);
-    // ZKLC_NTT_TILE=12|13 pins it (A/B).
-    static const int tile_pin = getenv("ZKLC_NTT_TILE") ? atoi(getenv("ZKLC_NTT_TILE")) : 0;
-    auto n_passes = [&](int T) { return 1 + (logn > T ? (logn - T + (T - 4) - 1) / (T - 4) : 0); };
-    int T = NTT_TILE_LOG_MAX;
-    if (!radix2 && (tile_pin == NTT_TILE_LOG_BIG || (tile_pin == 0 && n_passes(NTT_TILE_LOG_BIG) < n_passes(NTT_TILE_LOG_MAX))))
-        T = NTT_TILE_LOG_BIG;
-    int ks[8], np = 0;
-    int k_last = logn < T ? logn : T;
-    int remaining = logn - k_last;
-    for (int m = n_passes(T) - 1; m > 0; m--) {      // even split of the strided bits
-        int k = (remaining + m - 1) / m;
-        ks[np++] = k;
-        remaining -= k;
-    }
-    ks[np++] = k_last;
-    u64 n_inv = inverse ? host_gl_pow(1ULL << logn, GL_P - 2) : 1;
-    int s0_of[8], s0 = 0;
-    for (int i = 0; i < np; i++) {
-        s0_of[i] = s0;
-        s0 += ks[i];
-    }
-    // groups of <= 4 stages per pass (sizes as even as possible: 13 = 4 + 3 + 3 + 3) and their blocks in the twiddle table; the
-    // plan depends on logn only, so the table is built once per (logn, direction) and context
-    int ng_of[8], gsz_of[8][4];
-    u64 goff_of[8][4], tab_elems = 0;
-    for (int i = 0; i < np; i++) {
-        int ng = (ks[i] + 3) / 4, base = ks[i] / ng, extra = ks[i] % ng, t0 = 0;
-        ng_of[i] = ng;
-        for (int j = 0; j < ng; j++) {
-            int g = base + (j < extra ? 1 : 0);
-            gsz_of[i][j] = g;
-            goff_of[i][j] = tab_elems;
-            tab_elems += ((1ULL << g) - 1) << (logn - (s0_of[i] + t0) - g);
-            t0 += g;
-        }
-    }
-    if (g4) {
-        // resident per (context, logn, direction); built on first use.  The build is serialised and COMPLETE before the pointer is
-        // published (another host thread or stream of the same context must never see a half-built block)
-        static std::mutex twg_mutex;
-        std::lock_guard<std::mutex> twg_lock(twg_mutex);
-        void **slot = inverse ? &ctx->gl_twg_inv[logn] : &ctx->gl_twg_fwd[logn];
-        if (!*slot) {
-            void *fresh = nullptr;
-            ZKLC_HIP(ctx, hipMalloc(&fresh, tab_elems * 8));
-            void **build = &fresh;
-            u64 w = host_gl_pow(GL_POWER_OF_TWO_GENERATOR, 1ULL << (32 - logn));
-            if (inverse) w = host_gl_pow(w, GL_P - 2);
-            for (int i = 0; i < np; i++) {
-                int t0 = 0;
-                for (int j = 0; j < ng_of[i]; j++) {
-                    int g = gsz_of[i][j], sf = s0_of[i] + t0;
-                    u64 nj = 1ULL << (logn - sf - g), cnt = ((1ULL << g) - 1) * nj;
-                    hipLaunchKernelGGL(gl_group_twiddle_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st,
-                                       (u64 *)*build + goff_of[i][j], w, (u32)g, (u32)sf, nj);
-                    t0 += g;
+    const u64 *tw = nullptr;
+    const u64 n = 1ULL << logn;
+    if (family == GL_NTT_RADIX2)
+        rc = gl_ntt_get_table(ctx, st, family, logn, inverse, n / 2, [&](u64 *tab, u64 w) {
+            hipLaunchKernelGGL(gl_pow_table_kernel, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, st, tab, w, n / 2, (u64)1);
+        }, &tw);
+    else if (family == GL_NTT_R8)
+        rc = gl_ntt_get_table(ctx, st, family, logn, inverse, n, [&](u64 *tab, u64 w) {
+            hipLaunchKernelGGL(gl_staged_twiddle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tab, w, (u32)logn);
+        }, &tw);
+    else
+        rc = gl_ntt_get_table(ctx, st, family, logn, inverse, plan.table_elems, [&](u64 *tab, u64 w) {
+            for (int i = 0; i < plan.n_passes; i++) {      // one block per group, in the order of the plan
+                const ntt_pass &p = plan.pass[i].p;
+                int sf = p.s0;
+                for (int j = 0; j < p.ng; sf += p.gsz[j++]) {
+                    const u64 cnt = gl_ntt_group_block_elems(logn, sf, p.gsz[j]);
+                    hipLaunchKernelGGL(gl_group_twiddle_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, tab + p.goff[j], w,
+                                       (u32)p.gsz[j], (u32)sf, n >> (sf + p.gsz[j]));
                 }
             }
-            ZKLC_HIP(ctx, hipGetLastError());
-            ZKLC_HIP(ctx, zklc_stream_wait(st));       // once per (logn, direction)
-            *slot = fresh;
-        }
-        tw = (const u64 *)*slot;
-    }
-    for (int ii = 0; ii < np; ii++) {
-        int i = dit ? (np - 1 - ii) : ii;  // DIT runs the windows bottom-up
-        ntt_pass p;
-        p.logn = logn;
-        p.s0 = s0_of[i];
-        p.k = ks[i];
-        int lowbits = logn - p.s0 - p.k;
-        p.c = lowbits < (T - p.k) ? lowbits : (T - p.k);
-        int room = T - p.k - p.c;
-        p.d = p.s0 < room ? p.s0 : room;
-        bool first = (ii == 0), last = (ii == np - 1);
-        p.log_in = first ? log_in : logn;
-        p.scale_shift = (first && load_shift) ? GL_SCALE_LO_LOG : 0;
-        p.out_scale = last ? n_inv : 1;
-        static const bool zskip_on = !(getenv("ZKLC_NTT_ZSKIP") && getenv("ZKLC_NTT_ZSKIP")[0] == '0');
-        p.zskip_ok = zskip_on ? 1 : 0;
-        p.ng = ng_of[i];
-        for (int j = 0; j < 4; j++) {
-            p.gsz[j] = j < ng_of[i] ? gsz_of[i][j] : 0;
-            p.goff[j] = j < ng_of[i] ? goff_of[i][j] : 0;
-        }
-        const u64 *src = first ? in : out;
-        size_t sstride = first ? in_stride : out_stride;
-        dim3 grid((unsigned)(1ULL << (logn - (p.k + p.c + p.d))), batch);
-        if (g4) {
-            const int tile_log = p.k + p.c + p.d;
-            const unsigned threads = tile_log > NTT_TILE_LOG_MAX ? NTT_THREADS_MAX : NTT_THREADS;
-            const size_t lds = ((size_t(1) << tile_log) + (size_t(1) << tile_log) / 16) * sizeof(u64);
-            const u64 *sh = (const u64 *)ctx->gl_scale_hi, *sl = (const u64 *)ctx->gl_scale_lo;
-            void (*fn)(const u64 *, u64 *, size_t, size_t, ntt_pass, const u64 *, const u64 *, const u64 *);
-            if (zklc_lean_arith())
-                fn = dit ? (inverse ? gl_ntt_pass_g4_kernel<true, true, true> : gl_ntt_pass_g4_kernel<true, false, true>)
-                         : (inverse ? gl_ntt_pass_g4_kernel<false, true, true> : gl_ntt_pass_g4_kernel<false, false, true>);
-            else
-                fn = dit ? (inverse ? gl_ntt_pass_g4_kernel<true, true, false> : gl_ntt_pass_g4_kernel<true, false, false>)
-                         : (inverse ? gl_ntt_pass_g4_kernel<false, true, false> : gl_ntt_pass_g4_kernel<false, false, false>);
-            hipLaunchKernelGGL(fn, grid, dim3(threads), lds, st, src, out, sstride, out_stride, p, tw, sh, sl);
-        } else if (radix2) {
-            if (dit)
-                hipLaunchKernelGGL(gl_ntt_pass_kernel<true>, grid, dim3(NTT_THREADS), 0, st, src, out, sstride, out_stride, p, tw,
-                                   (const u64 *)ctx->gl_scale_hi, (const u64 *)ctx->gl_scale_lo);
-            else
-                hipLaunchKernelGGL(gl_ntt_pass_kernel<false>, grid, dim3(NTT_THREADS), 0, st, src, out, sstride, out_stride, p, tw,
-                                   (const u64 *)ctx->gl_scale_hi, (const u64 *)ctx->gl_scale_lo);
-        } else {
-            const int tile_log = p.k + p.c + p.d;
-            const unsigned threads = tile_log > NTT_TILE_LOG_MAX ? NTT_THREADS_MAX : NTT_THREADS;
-            const size_t lds = ((size_t(1) << tile_log) + (size_t(1) << tile_log) / 8) * sizeof(u64);
-            if (dit)
-                hipLaunchKernelGGL(gl_ntt_pass_r8_kernel<true>, grid, dim3(threads), lds, st, src, out, sstride, out_stride, p, tw,
-                                   (const u64 *)ctx->gl_scale_hi, (const u64 *)ctx->gl_scale_lo);
-            else
-                hipLaunchKernelGGL(gl_ntt_pass_r8_kernel<false>, grid, dim3(threads), lds, st, src, out, sstride, out_stride, p, tw,
-                                   (const u64 *)ctx->gl_scale_hi, (const u64 *)ctx->gl_scale_lo);
-        }
+        }, &tw);
+    if (rc) return rc;
+
+    const gl_ntt_pass_fn fn = gl_ntt_pass_kernel_of(family, dit, inverse, lean);
+    const u64 *sh = (const u64 *)ctx->gl_scale_hi, *sl = (const u64 *)ctx->gl_scale_lo;
+    for (int ii = 0; ii < plan.n_passes; ii++) {
+        int i;
+        const ntt_pass p = gl_ntt_plan_launch_pass(&plan, ii, dit, &i);   // DIT runs the windows bottom-up
+        const gl_ntt_plan_pass &pp = plan.pass[i];
+        const u64 *src = ii == 0 ? in : out;
+        const size_t sstride = ii == 0 ? in_stride : out_stride;
+        const size_t lds = family == GL_NTT_G4 ? pp.lds_g4 : family == GL_NTT_R8 ? pp.lds_r8 : 0;
+        hipLaunchKernelGGL(fn, dim3(pp.grid_x, batch), dim3(pp.threads), lds, st, src, out, sstride, out_stride, p, tw, sh, sl);
         ZKLC_HIP(ctx, hipGetLastError());
     }
     return ZKLC_OK;

@@ -9,7 +9,7 @@
 #include <string>
 #include "../../include/zklc.h"
 
-#define ZKLC_GL_MAX_LOG 24
+#include "gl_ntt_plan.h"   // ZKLC_GL_MAX_LOG
 
 struct zklc_devbuf {
     void *p = nullptr;
@@ -23,15 +23,9 @@ struct zklc_ctx {
     // Ed25519: 128 affine-niels multiples of the base point (12 KiB)
     void *ed_btab = nullptr;
     int ed_variant = 0;  // index into the compiled verify-kernel variants
-    // Goldilocks: twiddle tables w^i (i < 2^(logn-1)) per transform size, forward and inverse
-    void *gl_tw_fwd[ZKLC_GL_MAX_LOG + 1] = {};
-    void *gl_tw_inv[ZKLC_GL_MAX_LOG + 1] = {};
-    // staged tables (per stage s: w^(j << s) contiguous), used by the radix-8 passes
-    void *gl_tws_fwd[ZKLC_GL_MAX_LOG + 1] = {};
-    void *gl_tws_inv[ZKLC_GL_MAX_LOG + 1] = {};
-    // per-element group twiddles of the shift-twiddle passes (goldilocks_ntt_group.cuh): blocks w^((bitrev_g(m) J) << s') per group
-    void *gl_twg_fwd[ZKLC_GL_MAX_LOG + 1] = {};
-    void *gl_twg_inv[ZKLC_GL_MAX_LOG + 1] = {};
+    // Goldilocks NTT: the twiddle table of each pass-kernel family (goldilocks.hip: flat w^i for the radix-2 passes, staged per stage
+    // for the radix-8 passes, per-element group twiddles for the shift-twiddle passes) per direction (forward, inverse) and size
+    void *gl_ntt_tab[3][2][ZKLC_GL_MAX_LOG + 1] = {};
     // two-level table of coset-shift powers (shift^j = hi[j >> 10] * lo[j & 1023])
     void *gl_scale_hi = nullptr, *gl_scale_lo = nullptr;
     uint64_t gl_scale_shift = 0;
