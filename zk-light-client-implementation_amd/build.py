@@ -114,7 +114,37 @@ def build_poseidon_gate_dev(verbose=True, force=False):
     return PGD_LIB
 
 
+FCD_DIR = os.path.join(HERE, "..", "tests", "fri_coeff_dev")
+FCD_SRC = os.path.join(FCD_DIR, "fri_coeff_dev.hip")
+FCD_CASES = os.path.join(FCD_DIR, "fri_coeff_dev_cases.cpp")
+FCD_LIB = os.path.join(FCD_DIR, "libfri_coeff_dev.so")
+
+
+def fri_coeff_dev_is_current():
+    deps = [FCD_SRC, FCD_CASES, os.path.join(HERE, "..", "tests", "fri_coeff_host", "fri_coeff_cases.h"), os.path.abspath(__file__)]
+    deps += [p for ext in ("*.cuh", "*.h", "*.inc") for p in glob.glob(os.path.join(CSRC, ext))]
+    return os.path.exists(FCD_LIB) and os.path.getmtime(FCD_LIB) >= _newest(deps)
+
+
+def build_fri_coeff_dev(verbose=True, force=False):
+    """tests/fri_coeff_dev/libfri_coeff_dev.so: the coefficient-form FRI combination kernel over the cases of
+    tests/fri_coeff_host (test infrastructure for tests/test_gpu_fri_coeff.py; the kernel with the library's compiler and FLAGS, the
+    cases and their Horner sums as plain host C++; a few seconds)."""
+    if force or not fri_coeff_dev_is_current():
+        obj, kobj = os.path.join(FCD_DIR, "fri_coeff_dev_cases.o"), os.path.join(FCD_DIR, "fri_coeff_dev.o")
+        for cmd in ([HOST_CXX, "-O2", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-c", FCD_CASES, "-o", obj],
+                    [HIPCC] + FLAGS + ["-c", FCD_SRC, "-o", kobj],
+                    [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", FCD_LIB, kobj, obj]):
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError("%s failed for %s:\n%s\n%s" % (cmd[0], FCD_DIR, r.stdout[-4000:], r.stderr[-4000:]))
+        if verbose:
+            print("[zklc build] built", FCD_LIB, file=sys.stderr)
+    return FCD_LIB
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_devsim(force="--force" in sys.argv)
     build_poseidon_gate_dev(force="--force" in sys.argv)
+    build_fri_coeff_dev(force="--force" in sys.argv)

@@ -22,6 +22,7 @@
 #include "plonky2_gates.cuh"
 #include "plonky2_host.h"
 #include "plonky2_perm_terms.cuh"
+#include "plonky2_fri_combine.cuh"
 #include "zklc_internal.h"
 
 #define P2_THREADS 256
@@ -986,8 +987,10 @@ __global__ void __launch_bounds__(P2_THREADS) p2_fri_denominators_kernel(const u
 //   out(x) = alpha^nch * (sum_i alpha^i p_i(x) - y0) / (x - zeta) + (sum_{i<nch} alpha^i z_i(x) - y1) / (x - g zeta)
 // The sums are NOT evaluated by Horner's rule (one extension multiplication per polynomial and a dependency chain as long as
 // the list): alpha^i comes from a table of 22-bit limbs (p2_ext_pow_limbs_kernel) and every p_i(x) alpha^i is twelve carry-free
-// v_mad_u64_u32 into two column accumulators (gl_acc3_mul) -- ~4 k instructions per point for the 357 polynomials of the
-// Ed25519 circuit instead of ~30 k, which leaves the kernel to the 8 bytes per polynomial and point it has to read.
+// v_mad_u64_u32 into two column accumulators (p2_fri_alpha_sum, plonky2_fri_combine.cuh) -- ~4 k instructions per point for the
+// 357 polynomials of the Ed25519 circuit instead of ~30 k, which leaves the kernel to the 8 bytes per polynomial and point it
+// has to read.  This is the form ZKLC_P2_FRI_COMBINE=points and ZKLC_LEAN_ARITH=0 select; the default forms the same sums on the
+// coefficients (p2_fri_coeff_combine_kernel) and extends the result.
 //
 // LEAN: x from the circuit's table and the two inverse norms from p2_fri_denominators_kernel (in out[p]) instead of a gl_pow and two
 // base-field inversions -- ~300 multiply-reduces per point beside the combination itself; false = as it was (ZKLC_LEAN_ARITH=0).
@@ -1006,42 +1009,9 @@ __global__ void __launch_bounds__(P2_THREADS) p2_fri_combine_kernel(p2_fri_combi
         x = gl_mul(GL_GENERATOR, gl_pow(a.w_lde, i));
     }
     gl_acc3 sa = {0, 0, 0}, sb = {0, 0, 0};
-    gl_ktab *k6 = (gl_ktab *)a.apow;
-    u32 terms = 0;
-    for (int m = 0; m < 4; m++) {
-        const u64 *mat = a.mats[m] + p;
-        const u32 w = a.widths[m];
-        u32 j = 0;
-        for (; j + 16 <= w; j += 16, k6 += 16 * 12) {   // sixteen loads in flight
-            u64 v[16];
-#pragma unroll
-            for (int q = 0; q < 16; q++) v[q] = mat[(size_t)(j + q) * N];
-#pragma unroll
-            for (int q = 0; q < 16; q++) {
-                gl_acc3_mul(sa, v[q], k6 + 12 * q);
-                gl_acc3_mul(sb, v[q], k6 + 12 * q + 6);
-            }
-            if ((terms += 16) >= 384) {                  // a column holds 2^10 products = 512 terms; the tails below add < 48
-                terms = 0;
-                gl_acc3_normalize(sa);
-                gl_acc3_normalize(sb);
-            }
-        }
-        for (; j < w; j++, k6 += 12) {
-            u64 v = mat[(size_t)j * N];
-            gl_acc3_mul(sa, v, k6);
-            gl_acc3_mul(sb, v, k6 + 6);
-        }
-        terms += 16;
-    }
+    p2_fri_alpha_sum(a.mats, a.widths, N, p, (gl_ktab *)a.apow, sa, sb);
     gl2 acc = gl2_make(gl_acc3_reduce(sa), gl_acc3_reduce(sb));
-    gl_acc3 ta = {0, 0, 0}, tb = {0, 0, 0};
-    for (u32 j = 0; j < a.nch; j++) {
-        u64 v = a.mats[2][(size_t)j * N + p];
-        gl_acc3_mul(ta, v, (gl_ktab *)a.apow + 12 * (size_t)j);
-        gl_acc3_mul(tb, v, (gl_ktab *)a.apow + 12 * (size_t)j + 6);
-    }
-    gl2 acc1 = gl2_make(gl_acc3_reduce(ta), gl_acc3_reduce(tb));
+    gl2 acc1 = p2_fri_zs_sum(a.mats[2], a.nch, N, p, (gl_ktab *)a.apow);
     gl2 i0, i1;
     if constexpr (LEAN) {
         i0 = p2_fri_den_inverse(x, a.zeta, ninv.a);
@@ -1199,6 +1169,7 @@ struct zklc_plonky2_circuit {
     std::vector<double> gate_ms;      // calibration: per-gate kernel time (the last entry is the base kernel)
     gl2 *d_zpow = nullptr, *d_open = nullptr, *d_open_partial = nullptr;
     gl2 *d_fri[9] = {};               // FRI oracles (extension values), [0] has N elements
+    u64 *d_fri_gh = nullptr, *d_fri_gh_lde = nullptr;   // coefficient-form FRI combination: [G.a, G.b, H.a, H.b] x n, and x N
     u64 *d_fri_tree[8] = {};
     gl2 *d_final = nullptr;
     unsigned long long *d_found = nullptr;
@@ -1273,6 +1244,13 @@ static void p2_pin_reset(zklc_plonky2_circuit *c) {
         (c)->ctx->last_err = "hipHostMalloc: pinned staging";                 \
         return ZKLC_ERR_OOM;                                                  \
     }
+
+// The FRI opening combination is formed on the coefficients (plonky2_fri_combine.cuh) whenever the lean arithmetic is on;
+// ZKLC_P2_FRI_COMBINE=points keeps the kernel that sums at every LDE point (A/B and the parity test).  Read once per process.
+static bool p2_fri_combine_on_coeffs() {
+    static const bool on = zklc_lean_arith() && !(getenv("ZKLC_P2_FRI_COMBINE") && !strcmp(getenv("ZKLC_P2_FRI_COMBINE"), "points"));
+    return on;
+}
 
 static int32_t p2_alloc(zklc_plonky2_circuit *c, void **p, size_t bytes) {
     zklc_ctx *ctx = c->ctx;
@@ -1540,6 +1518,12 @@ static int32_t p2_create(zklc_ctx *ctx, const zklc_plonky2_params *params, const
     // FRI oracles
     u32 bits = c->lde_bits;
     P2_ALLOC(c, c->d_fri[0], (size_t)N * sizeof(gl2));
+    if (p2_fri_combine_on_coeffs()) {      // 4 n + 4 N words (8 MB + 64 MB at 2^18 rows, rate 3)
+        P2_ALLOC(c, c->d_fri_gh, (size_t)4 * n * 8);
+        P2_ALLOC(c, c->d_fri_gh_lde, (size_t)4 * N * 8);
+    }
+    if (getenv("ZKLC_P2_DEBUG"))
+        fprintf(stderr, "[zklc] fri combine: %s\n", p2_fri_combine_on_coeffs() ? "coefficients" : zklc_lean_arith() ? "points" : "points, as it was");
     for (u32 r = 0; r < P.num_arities; r++) {
         u32 leaves_bits = bits - P.arity_bits[r];
         u32 cap_h = P.cap_height < leaves_bits ? P.cap_height : leaves_bits;
@@ -1924,7 +1908,36 @@ extern "C" int32_t zklc_plonky2_prove_dev(zklc_ctx *ctx, void *stream, zklc_plon
             const u32 lanes = (N + P2_FRI_DEN_POINTS - 1) / P2_FRI_DEN_POINTS;
             hipLaunchKernelGGL(p2_fri_denominators_kernel, dim3((lanes + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st,
                                (const u64 *)c->d_xs, c->lde_bits, a.zeta, a.g_zeta, a.out);
-            hipLaunchKernelGGL(p2_fri_combine_kernel<true>, dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
+            if (p2_fri_combine_on_coeffs()) {
+                // G = sum_i alpha^i p_i and H = sum_{i<nch} alpha^i z_i on the coefficients every batch still holds (the openings
+                // above read them), one LDE of their four base-field columns, then the two divisions point by point
+                p2_fri_coeff_args ca = {};
+                const p2_batch *bs[4] = {&c->cs, &c->wires, &c->zs, &c->quot};
+                for (int k = 0; k < 4; k++) {
+                    ca.coeffs[k] = bs[k]->coeffs;
+                    ca.widths[k] = bs[k]->width;
+                }
+                ca.n = n;
+                ca.nch = nch;
+                ca.apow = c->d_fri_apow;
+                ca.out = c->d_fri_gh;
+                hipLaunchKernelGGL(p2_fri_coeff_combine_kernel, dim3((n + P2_FRI_THREADS - 1) / P2_FRI_THREADS), dim3(P2_FRI_THREADS), 0, st, ca);
+                ZKLC_HIP(ctx, hipGetLastError());
+                P2_RC(zklc_gl_lde_dev(ctx, st, c->d_fri_gh, P.degree_bits, P.rate_bits, 4, GL_GENERATOR, c->d_fri_gh_lde, ZKLC_NTT_OUT_BITREV));
+                p2_fri_finish_args fa = {};
+                fa.gh = c->d_fri_gh_lde;
+                fa.xs = c->d_xs;
+                fa.lde_bits = c->lde_bits;
+                fa.zeta = a.zeta;
+                fa.g_zeta = a.g_zeta;
+                fa.y0 = a.y0;
+                fa.y1 = a.y1;
+                fa.alpha_pow_nch = a.alpha_pow_nch;
+                fa.out = a.out;
+                hipLaunchKernelGGL(p2_fri_coeff_finish_kernel, dim3((N + P2_FRI_THREADS - 1) / P2_FRI_THREADS), dim3(P2_FRI_THREADS), 0, st, fa);
+            } else {
+                hipLaunchKernelGGL(p2_fri_combine_kernel<true>, dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
+            }
         } else {
             hipLaunchKernelGGL(p2_fri_combine_kernel<false>, dim3((N + P2_THREADS - 1) / P2_THREADS), dim3(P2_THREADS), 0, st, a);
         }
